@@ -7,7 +7,11 @@ Workload W3 (BASELINE config #3): Qwen3-TTS-1.7B-shaped talker, rando
 whole decode step (code predictor + 28-layer backbone + lm_head + sampler) captured as ONE hipGraph.
 A "step" = one decode step of the batch = 64 speech tokens (64 codec frames of 16 codes).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, ms_per_step, the roofline figure that
+is arithmetic on the timed steps).  --dump-outputs DIR also writes what the last timed step handed its caller as DIR/<name>.npy.
+--full adds every other leg, none of them part of `value`: TTFA (timed prefill + first chunk), the all-reduce cost per launch,
+backbone-only and per-family replays, the replica leg (N > 1), the PMC traffic figure, the copy probe, the engine loop and the CPU oracle.
 N > 1 without WORLD_SIZE in the environment: this process (which has made no GPU call) starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child, relays rank 0's JSON line and exits with
 the child's code; under torchrun (WORLD_SIZE set) each rank runs the tensor-parallel step over RCCL (strong scaling).
@@ -230,6 +234,21 @@ def engine_loop(d, w, args, lens, async_on, n_steps=200):
     return res
 
 
+def dump_outputs(eng, B, path):
+    """What the last timed decode step handed its caller, as <path>/<name>.npy: the step's output record (sampled ids, the 16-code
+    frames, the hidden states h[t]) and the logits the ids were drawn from -- 64 rows, 1 MB in all, so no sampling of rows is needed.
+    Integers are exact in float64; bf16 and fp32 values are exact in float32.  Masked logits are -inf on the device: they are stored
+    as -1e9 (the finite suppression value of the Omni talker's mask) so that two dumps can be subtracted."""
+    os.makedirs(path, exist_ok=True)
+    logits = eng.logits[:B].cpu().to(torch.float32)
+    arrays = {"token_ids": eng.input_ids[:B].cpu().to(torch.float64),
+              "audio_codes": eng.audio_codes[:B].cpu().to(torch.float64),
+              "last_hidden": eng.last_hidden[:B].cpu().to(torch.float32),
+              "logits": torch.where(torch.isneginf(logits), torch.full_like(logits, -1e9), logits)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
 def copy_probe_gbs():
     """Achievable HBM bandwidth: device-to-device copy of 1 GiB (read + write bytes / time)."""
     n = 1 << 30
@@ -256,6 +275,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last timed step's outputs "
+                    "(sampled ids, code frames, hidden states, logits) as DIR/<name>.npy; same arguments, same inputs, run after run")
+    ap.add_argument("--full", action="store_true", help="also run the legs that are no part of `value`: TTFA, all-reduce cost, "
+                    "backbone-only / per-family replays, replica leg, PMC traffic, copy probe, engine loop, CPU oracle (the --no-* "
+                    "options below drop single legs of a --full run)")
     ap.add_argument("--model", default="tts-1.7b")
     ap.add_argument("--kv", default="fp8")
     ap.add_argument("--batch", type=int, default=64)
@@ -349,7 +373,8 @@ def main():
     else:
         eng.set_sampling(greedy=0, temperature=0.9, top_k=50, rep_penalty=1.05, seed=42, cp_greedy=0, cp_temperature=0.9,
                          cp_top_k=50)
-    setup_requests(d, eng, args)                 # untimed: hipBLASLt handle / heuristics, code objects
+    if args.full:                                # TTFA times a warm prefill: a first, unclocked pass takes the hipBLASLt handle /
+        setup_requests(d, eng, args)             # heuristics and the code objects (it leaves the state the second pass starts from)
     lens, prefill_ms = setup_requests(d, eng, args)
     log(f"[rank {rank}] prefill of {sum(lens)} prompt tokens: {prefill_ms:.1f} ms ({'omni_gemm_tile (hand-written MFMA)' if args.prefill_gemm == 'tile' else 'hipBLASLt'} GEMMs + native norm/rope/attention)")
 
@@ -374,14 +399,17 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- TTFA: prefill + IC decode steps (IC = 16 at full load), vocoder / HTTP excluded
+    # ---- TTFA: prefill + IC decode steps (IC = 16 at full load), vocoder / HTTP excluded.  The IC steps are part of
+    # the step sequence of every run (the timed steps see the same state with and without --full); only --full puts a clock on them
     steps_done = 2 if graph is not None else 1
     n_ic = max(args.ttfa_steps - steps_done, 2)      # at IC = 2 (B = 1) both steps are already behind us: time two more
-    sync()
+    if args.full:
+        sync()
     t0 = time.perf_counter()
     for _ in range(n_ic):
         run()
-    sync()
+    if args.full:
+        sync()
     ic_ms = (time.perf_counter() - t0) * 1e3 / n_ic * args.ttfa_steps
     ttfa_ms = prefill_ms + ic_ms
 
@@ -425,12 +453,14 @@ def main():
     if dev_err:
         log(f"[rank {rank}] in-kernel hand-off timed out during the timed region (code {dev_err}: 1 = chain flags, 2 = peer all-reduce): result void")
         sys.exit(3)
+    if args.dump_outputs and rank == 0:          # before any other leg touches the engine's buffers
+        dump_outputs(eng, B, args.dump_outputs)
 
     # ---- tensor-parallel ranks: what ONE all-reduce of the step costs on this node, and which one ran (the first
     # 8-GPU run must say where its time went).  After the timed region, every rank in lock-step: 2 x layers launches of the step's
     # own all-reduce -- the one-shot kernel over the peer-mapped buffers (fused residual add + slabs), or RCCL on the [B, H] message
     ar_diag = None
-    if dist is not None and args.parallel == "tp":
+    if args.full and dist is not None and args.parallel == "tp":
         try:
             n_ar = 2 * d.layers
             sync()
@@ -484,7 +514,7 @@ def main():
 
     # ---- diagnostics (after the timed region): the backbone half of the step alone, as its own graph
     bb_ms = None
-    if graph is not None and world == 1 and args.sub_batches == 1 and not args.tp_force and not args.no_diagnostics:
+    if args.full and graph is not None and world == 1 and args.sub_batches == 1 and not args.tp_force and not args.no_diagnostics:
         try:
             g2 = torch.cuda.CUDAGraph()
             eng.backbone_step(B)
@@ -507,7 +537,7 @@ def main():
     # as its own hipGraph and replayed alone (omni_talker_step_part).  A part run alone reads whatever the buffers hold: its time is
     # the step's, its outputs are not -- this engine's request state is void from here on (the replica leg builds its own).
     families = None
-    if graph is not None and world == 1 and args.sub_batches == 1 and not args.tp_force and not args.no_diagnostics:
+    if args.full and graph is not None and world == 1 and args.sub_batches == 1 and not args.tp_force and not args.no_diagnostics:
         try:
             split = bool(chains_ran & 2)
             plan = [("code_predictor_phase_ms", 1)] + ([("backbone_attention_ms", 2), ("backbone_chain_ms", 4)] if split else [("backbone_stack_ms", 6)]) \
@@ -575,7 +605,7 @@ def main():
                    "sampling": "greedy" if args.greedy else "T=0.9,top_k=50,rep=1.05,seed=42",
                    "target_ctx": args.target_ctx, "untimed_advance_steps": advance,
                    **({"ctx_extra": args.ctx_extra} if args.ctx_extra else {})},
-        "p50_ttfa_ms": ttfa_ms, "ttfa": {"prefill_ms": prefill_ms, "ic_steps": args.ttfa_steps, "ic_ms": ic_ms},
+        **({"p50_ttfa_ms": ttfa_ms, "ttfa": {"prefill_ms": prefill_ms, "ic_steps": args.ttfa_steps, "ic_ms": ic_ms}} if args.full else {}),
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                      "launch": "one hipGraph replay = one decode step (per TP rank)", "event_ms_per_step": ev_ms,
@@ -597,7 +627,7 @@ def main():
     # ---- second leg (N > 1, tensor-parallel runs only; never part of `value`): the same step as independent replicas --
     # one full engine per GPU, 64 requests each, no data-path collective -- so the line carries both axes of SURVEY 8e.
     # Every rank makes the same collective calls whether or not its local part succeeded.
-    if dist is not None and args.parallel == "tp" and not args.no_replica_leg:
+    if args.full and dist is not None and args.parallel == "tp" and not args.no_replica_leg:
         ok, dt_r, run2 = 1, 0.0, None
         try:
             graph = None
@@ -636,7 +666,7 @@ def main():
                                "note": "same step, one full engine and 64 requests per GPU, no data-path collective; "
                                        "second leg of this run, not part of `value`"}
         eng = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # HBM bytes per step from the PMC passes (rocprofv3 cannot ride along with a timed run: separate
         # --pmc FETCH_SIZE / WRITE_SIZE passes of this same command, summary committed under profiles/)
         # `traffic` stays null unless a committed PMC summary of this same command exists AT THIS CONTEXT (within 5 %);
@@ -690,6 +720,7 @@ def main():
             except Exception as e:   # noqa: BLE001
                 log(f"cpu baseline failed: {e!r}")
                 out["cpu_baseline"] = None
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if dist is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # other configurations of BASELINE.json / SURVEY 8d next to the headline W3 line (one JSON line each into gpurun_out/)
 cd "$GRAFT_REPO_ROOT"
-run() { tag=$1; shift; python bench.py --no-cpu-baseline --no-engine-loop "$@" 2>/dev/null | python -c "
+run() { tag=$1; shift; python bench.py --full --no-cpu-baseline --no-engine-loop "$@" 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read()); r=j['roofline']; b=r.get('breakdown') or {}
 print('$tag', 'ms/step %.3f' % j['ms_per_step'], 'tok/s %.0f' % j['value'], 'frac %.3f' % r['frac'], 'ctx %.0f' % j['config']['mean_ctx'], 'ttfa %.1f' % j['p50_ttfa_ms'], 'bb_ms %.3f bb_frac %.3f' % (b.get('backbone_ms', 0), b.get('backbone_frac', 0)))"; }
 run W3-fp8 --steps 128

@@ -1,4 +1,4 @@
-"""The bench line the driver parses (the committed run of the current build, profiles/): every field of the contract."""
+"""The bench line the driver parses (the committed `bench.py --full` run of the current build, profiles/): every field of the contract."""
 import glob
 import json
 import os
@@ -78,3 +78,31 @@ def test_bench_gpus_n_relays_the_childs_json_line(tmp_path):
     stub.write_text("import sys\nprint('{\"value\": 1}')\nsys.exit(7)\n")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 7 and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_the_output_record_as_float_arrays(tmp_path):
+    """--dump-outputs: ids, code frames, hidden states and logits of the step as DIR/<name>.npy in float32 / float64, integers and
+    bf16 values exact, every entry finite (masked logits are -inf on the device) so that two builds' dumps can be subtracted."""
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+
+    import bench
+    g = torch.Generator().manual_seed(0)
+    Bm, B, Q, H, V = 6, 4, 16, 32, 48
+    logits = torch.randn(Bm, V, generator=g)
+    logits[:, 40:] = float("-inf")
+    eng = SimpleNamespace(input_ids=torch.randint(0, 3072, (Bm,), generator=g, dtype=torch.int32),
+                          audio_codes=torch.randint(0, 2048, (Bm, Q), generator=g, dtype=torch.int64),
+                          last_hidden=torch.randn(Bm, H, generator=g).to(torch.bfloat16), logits=logits)
+    out = tmp_path / "dump" / "nested"
+    bench.dump_outputs(eng, B, str(out))
+    got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["audio_codes", "last_hidden", "logits", "token_ids"]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert np.array_equal(got["token_ids"], eng.input_ids[:B].numpy()) and got["token_ids"].shape == (B,)
+    assert np.array_equal(got["audio_codes"], eng.audio_codes[:B].numpy()) and got["audio_codes"].shape == (B, Q)
+    assert np.array_equal(got["last_hidden"], eng.last_hidden[:B].float().numpy())
+    assert np.array_equal(got["logits"][:, :40], logits[:B, :40].numpy()) and (got["logits"][:, 40:] == -1e9).all()
