@@ -497,10 +497,12 @@ class TalkerOracle:
 
     def code_predictor(self, layer0_code: torch.Tensor, layer0_embed: torch.Tensor, last_hidden: torch.Tensor,
                        *, do_sample: bool = False, temperature: float = 0.9, top_k: int = 50, top_p: float = 1.0,
-                       seed: int = 0, step: int = 0, return_logits: bool = False):
+                       seed: int = 0, step: int = 0, return_logits: bool = False, forced_codes: torch.Tensor | None = None):
         """layer0_code [B] int64, layer0_embed [B,H] bf16, last_hidden [B,H] bf16 -> all_codes [B,Q].
         Sampling uses this oracle's hash RNG (the reference uses torch.multinomial on the
-        global generator, code_predictor_vllm.py:545-551: not reproducible -> greedy for parity)."""
+        global generator, code_predictor_vllm.py:545-551: not reproducible -> greedy for parity).
+        forced_codes [B,Q] (test infrastructure, teacher forcing): group g's pick -- what goes into `codes` and, embedded, into the
+        next pass's input -- is forced_codes[:, g] whatever the logits say, so that two arithmetics can be compared on one frame."""
         d, w = self.d, self.w
         B, Q = layer0_code.shape[0], d.num_code_groups
         codes = torch.empty(B, Q, dtype=torch.long)
@@ -520,6 +522,8 @@ class TalkerOracle:
                                                top_k=top_k, top_p=top_p, seed=int(sd[b]), step=int(st[b]) * Q + g) for b in range(B)])
             else:
                 nxt = logits.argmax(-1)
+            if forced_codes is not None:
+                nxt = forced_codes[:, g].to(torch.long)
             codes[:, g] = nxt
             if g < Q - 1:
                 buf[:, g + 1] = self.cp_project(w["cp.embed"][g - 1][nxt])

@@ -70,7 +70,8 @@ def test_chain_is_bit_identical_to_the_launch_chain(model, B, mode):
 
 
 def test_chain_matches_oracle_at_full_predictor_depth():
-    """Product library, chain on (the default): greedy codes / logits of the 5-layer, 16-group predictor vs the oracle."""
+    """Product library, chain on (the default): greedy codes / group-1 logits of the 5-layer, 16-group predictor vs the oracle.  (Groups
+    2-15: the three-way accuracy gate of tests/test_gpu_predictor_accuracy.py.)"""
     d = get_dims("tts-1.7b").with_(layers=1, max_model_len=256)
     w = make_weights(d, seed=21, std=0.02)
     B = 48
@@ -79,7 +80,8 @@ def test_chain_matches_oracle_at_full_predictor_depth():
     codes, lg = eng.code_predictor(code0.to(torch.int32).cuda(), e0.cuda(), lh.cuda(), greedy=True, return_logits=True)
     assert eng.chain_error() == 0
     ref_codes, ref_lg = O.TalkerOracle(d, w).code_predictor(code0, e0, lh, do_sample=False, return_logits=True)
-    assert_e2e_close(lg.cpu()[:, 0], ref_lg[:, 0], mean_tol=6e-3, max_ulps=3, what="chain: code predictor logits, group 1 (5 layers)")
+    assert_e2e_close(lg.cpu()[:, 0], ref_lg[:, 0], mean_tol=6e-3, max_ulps=3, what="chain: code predictor logits, group 1 (5 layers)",
+                     deferred_rstd=True)      # qkv / gate_up stages of cp_pair_kernel (DEFER)
     assert (codes.cpu()[:, 1] == ref_codes[:, 1]).float().mean().item() >= 0.9
 
 

@@ -233,6 +233,15 @@ def test_slot_mapping_bit_exact(ops):
     assert got.tolist() == ref
 
 
+# K against the ORACLE's norm + RoPE (another summation order of the norm statistics: a rare 1-ulp bf16 flip of K before the quantiser):
+# 2 x the largest figure measured over the three head shapes below, never above the 0.01 / 1e-2 of rounds 1-6.  Measured:
+# NO fp8 K byte and NO int8 K scale differs from the oracle's on any of the three shapes (the kernel's 16-lane sum of squares lands on the
+# oracle's bf16 K for these inputs), so 2 x 0: the budgets are gone and equality is asserted.  The +-1 int8 count stays as the stated
+# distance of a K that did flip.  Given the kernel's own bf16 K the bytes are equal by construction: tests/test_gpu_parity_full.py.
+K_FP8_MISMATCH = 0.0
+K_INT8_SCALE_RTOL = 0.0
+
+
 @pytest.mark.parametrize("kv", ["bf16", "fp8", "int8"])
 @pytest.mark.parametrize("hq,hkv", [(4, 2), (16, 8), (2, 1)])
 def test_qknorm_rope_kvwrite(ops, kv, hq, hkv):
@@ -271,14 +280,17 @@ def test_qknorm_rope_kvwrite(ops, kv, hq, hkv):
         ref = pk.data.view(torch.uint8)
         assert torch.equal(got[1], ref[1]), "V fp8 bytes must be bit-exact (same input, RNE + saturate)"
         mism = (got[0] != ref[0]).float().mean().item()
-        assert mism < 0.01, f"K fp8 bytes differ in {mism:.3%}"
+        print(f"K fp8 byte mismatch ({hq}, {hkv}): {mism:.6f}")
+        assert mism <= K_FP8_MISMATCH, f"K fp8 bytes differ in {mism:.3%}"
         d = (got[0].view(torch.float8_e4m3fn).float() - ref[0].view(torch.float8_e4m3fn).float()).abs()
         assert (d <= ref[0].view(torch.float8_e4m3fn).float().abs() * 0.126 + 2 ** -9).all(), "K fp8 beyond 1 ulp"
     else:
         assert torch.equal(got[1], pk.data[1]), "V int8 must be bit-exact"
         assert torch.equal(scales.cpu()[1], pk.scales[1]), "V int8 scales must be bit-exact"
         assert (got[0].int() - pk.data[0].int()).abs().max().item() <= 1
-        torch.testing.assert_close(scales.cpu()[0], pk.scales[0], rtol=1e-2, atol=0)
+        dev = ((scales.cpu()[0] - pk.scales[0]).abs() / pk.scales[0].clamp_min(1e-30))[pk.scales[0] > 0].max().item()
+        print(f"K int8 scale deviation ({hq}, {hkv}): {dev:.6f}")
+        torch.testing.assert_close(scales.cpu()[0], pk.scales[0], rtol=K_INT8_SCALE_RTOL, atol=0)
     # padded token (slot -1) must not have been written anywhere: blocks 0 and 2's tail stay zero
     assert got[:, 0].abs().sum().item() == 0
 

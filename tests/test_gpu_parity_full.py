@@ -150,7 +150,8 @@ def test_full_depth_b64_persistent_chains_against_bf16_and_fp32_oracles(calibrat
       * code predictor: ALL 15 groups of all 64 rows against the oracle's greedy codes -- a row may leave the oracle's path only at
         a group whose two best logits are a near-tie (checked on the oracle's logits of that group); at least half the rows agree
         on the whole frame; and for EVERY group index the rows still on the oracle's path agree at that group in >= 85 % of cases
-        and their group logits meet the end-to-end bound (a broken stage of any pass would show at its group).
+        (a broken stage of any pass would show at its group).  The group LOGITS are not read here: their accuracy at every group
+        is the three-way statement of tests/test_gpu_predictor_accuracy.py (the same kernels at 49 and 17 rows, no backbone behind).
     calculate_kv_scales: the same with the fp8 scales set per layer by the prefill pass (max|k| / 200, max|v| / 100: NON-unit scales
     through the chained decode step, which reads them from the device table), oracles likewise.
     Reference: qwen3_tts_talker.py:414-443, qwen3_tts_code_predictor_vllm.py:480-561, gpu_ar_model_runner.py:122,269-275."""
@@ -468,3 +469,82 @@ def test_device_kv_write_bytes_match_the_format_definitions(golden_dir):
                 assert torch.equal(sl, slots)
             torch.cuda.synchronize()
             check(vc, vsc, z[key], z["int8_scale_v"] if code == L.KV_INT8 else None, f"{kvname} via {kernel}")
+
+
+# ------------------------------------------------------------------ the K-side quantiser, byte for byte
+@pytest.mark.parametrize("hq,hkv", [(4, 2), (16, 2)])
+@pytest.mark.parametrize("kernel", ["kvwrite", "decode"])
+def test_device_k_quantiser_bytes_given_the_kernels_own_bf16_k(kernel, hq, hkv):
+    """The G3 test pins the V bytes; K reaches the quantiser behind the q/k-norm and RoPE, and every other test gives its bytes a
+    mismatch budget (the norm sums in another order than the oracle's).  Both write kernels round K to bf16 BEFORE they quantise
+    (csrc/rope_kv.hip, pa_body.cuh), so the budget is not needed to isolate the quantiser: the same call into a bf16 cache yields the
+    kernel's own bf16 K (pinned to HF by the G2 test above), and the fp8 / int8 bytes -- and the int8 per-row scales -- the same call
+    stores must EQUAL O.PagedKV.write of exactly those rows: fp8 at k_scale 1 / 0.5 / 0.3 (a quotient that needs the correctly rounded
+    divide) / 2^-9 (saturation at +-448), int8 with one all-zero K head (amax clamps to 1e-8).  Slots 15 / 16 / 17 of a block, one
+    padded token (prefill-side kernel), non-identity norm weights; every slot not written stays zero."""
+    from ht_vllm_omni_amd import ops
+    D, T, bs, per_row = 128, 11, 16, 6
+    positions = [0, 1, 15, 16, 17, 40, 41, 95, 5, 6, 7]
+    g = torch.Generator().manual_seed(100 * hq + hkv)
+    qkv = (torch.randn(T, (hq + 2 * hkv) * D, generator=g) * 2.0).to(BF16)
+    qkv[3, (hq + 1) * D:(hq + 2) * D] = 0                                   # token 3, K head 1: an all-zero row
+    qn = (1 + 0.1 * torch.randn(D, generator=g)).to(BF16).cuda()
+    kn = (1 + 0.1 * torch.randn(D, generator=g)).to(BF16).cuda()
+    vv = qkv[:, (hq + hkv) * D:].reshape(T, hkv, D)
+    nb = 1 + T * per_row
+    bt = torch.tensor([[1 + r * per_row + j for j in range(per_row)] for r in range(T)], dtype=torch.int32)     # every token a request of its own
+    slots = torch.tensor([int(bt[r, p // bs]) * bs + p % bs for r, p in enumerate(positions)], dtype=torch.int64)
+    if kernel == "kvwrite":
+        slots[7] = -1                                                       # one padded token
+    live = slots >= 0
+    assert int(slots.max()) < nb * bs and {15, 0, 1} <= {int(s) % bs for s in slots[live]}
+    pos = torch.tensor(positions, dtype=torch.int32).cuda()
+    cos_sin = ops.rope_table(128, D, 1e6).cuda()
+    qkv_d, bt_d, slots_d = qkv.cuda().contiguous(), bt.cuda(), slots.cuda()
+
+    def run(code, store, k_scale):
+        kc = torch.zeros(nb, bs, hkv, D, dtype=store, device="cuda")
+        vc = torch.zeros_like(kc)
+        ksc = torch.zeros(nb, bs, hkv, dtype=torch.float32, device="cuda") if code == L.KV_INT8 else None
+        vsc = torch.zeros_like(ksc) if ksc is not None else None
+        if kernel == "kvwrite":
+            ops.qknorm_rope_kvwrite(qkv_d, qn, kn, pos, cos_sin, slots_d, kc, vc, q_heads=hq, kv_heads=hkv, head_dim=D, eps=1e-6,
+                                    kv_dtype=code, k_scale=k_scale, v_scale=1.0, k_scales=ksc, v_scales=vsc)
+        else:       # max_seq_len 128: the paged decode kernel of the product step (<= 64 would take the small-context kernel for bf16)
+            _, sl = ops.attn_decode_fused(qkv_d, qn, kn, pos, cos_sin, kc, vc, bt_d, pos + 1, q_heads=hq, kv_heads=hkv, head_dim=D,
+                                          block_size=bs, kv_dtype=code, eps=1e-6, k_scale=k_scale, v_scale=1.0, k_scales=ksc,
+                                          v_scales=vsc, max_seq_len=128)
+            assert torch.equal(sl.cpu(), slots)
+        torch.cuda.synchronize()
+        return kc.cpu(), vc.cpu(), None if ksc is None else ksc.cpu()
+
+    kc16, _, _ = run(L.KV_BF16, BF16, 1.0)
+    k_bf16 = torch.zeros(T, hkv, D, dtype=BF16)
+    k_bf16[live] = kc16.reshape(nb * bs, hkv, D)[slots[live]]
+    assert float(k_bf16[live].float().abs().max()) > 1.0 and int((k_bf16[3, 1] != 0).sum()) == 0
+    untouched = torch.ones(nb * bs, dtype=torch.bool)
+    untouched[slots[live]] = False
+    assert int(kc16.reshape(nb * bs, -1)[untouched].view(torch.int16).ne(0).sum()) == 0
+
+    for name, code, store, k_scale in (("fp8", L.KV_FP8, torch.uint8, 1.0), ("fp8", L.KV_FP8, torch.uint8, 0.5), ("fp8", L.KV_FP8, torch.uint8, 0.3),
+                                       ("fp8", L.KV_FP8, torch.uint8, 2.0 ** -9), ("int8", L.KV_INT8, torch.int8, 1.0)):
+        what = f"{name} k_scale {k_scale:g} via {kernel}, {hq} q / {hkv} kv heads"
+        kc, vc, ksc = run(code, store, k_scale)
+        pk = O.PagedKV(nb, bs, hkv, D, name, k_scale, 1.0)
+        pk.write(slots, k_bf16, vv)
+        if name == "fp8":
+            want = pk.data.view(torch.uint8)
+            for got, ref, side in ((kc, want[0], "K"), (vc, want[1], "V")):
+                nz = (ref & 0x7F) != 0                                      # +-0 both store a zero
+                assert torch.equal(got[nz], ref[nz]), f"{what}: {side} bytes differ in {int((got[nz] != ref[nz]).sum())} places"
+                assert bool(((got[~nz] & 0x7F) == 0).all()), f"{what}: {side} zeros"
+            if k_scale == 2.0 ** -9:
+                sat = float(((want[0].reshape(nb * bs, -1)[slots[live]] & 0x7F) == 0x7E).float().mean())
+                assert sat > 0.3, f"{what}: the case must saturate ({sat:.2f} of the K bytes at +-448)"
+        else:
+            assert torch.equal(kc, pk.data[0]), f"{what}: K counts differ in {int((kc != pk.data[0]).sum())} places"
+            assert torch.equal(vc, pk.data[1]), f"{what}: V counts"
+            assert torch.equal(ksc, pk.scales[0]), f"{what}: K scales"
+            zrow = ksc.reshape(nb * bs, hkv)[slots[3], 1]
+            assert float(zrow) == float(torch.tensor(1e-8, dtype=torch.float32) / 127.0), f"{what}: scale of the all-zero K row {float(zrow)}"
+        assert int(kc.reshape(nb * bs, -1)[untouched].view(torch.uint8).ne(0).sum()) == 0, f"{what}: another slot was written"

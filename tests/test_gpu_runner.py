@@ -80,7 +80,7 @@ def test_worker_runner_matches_oracle(graphs):
         for j, k in enumerate(keys):
             i = out.req_id_to_index[k]
             if codes_on_the_oracles_frame(out.pooler_output[i]["audio_codes"], oc[j:j + 1], orc.last_cp_logits[j:j + 1], what=f"{k}: audio codes")[0]:
-                assert_e2e_close(out.pooler_output[i]["hidden"], oh[j:j + 1], mean_tol=6e-3, what=f"{k} hidden")
+                assert_e2e_close(out.pooler_output[i]["hidden"], oh[j:j + 1], mean_tol=6e-3, what=f"{k} hidden", deferred_rstd=True)      # a decode step's qkv / gate_up (gemm.hip PRO 3)
             got = out.sampled_token_ids[i][0]
             if got != int(oi[j]):
                 top = torch.topk(ol[j], 2).values
@@ -208,7 +208,7 @@ def test_mixed_sampling_batch_with_prefill_inside_padded_bucket(graphs):
         for j, k in enumerate(keys):
             i = out.req_id_to_index[k]
             if codes_on_the_oracles_frame(out.pooler_output[i]["audio_codes"], oc[j:j + 1], orc.last_cp_logits[j:j + 1], what=f"{k}: audio codes")[0]:
-                assert_e2e_close(out.pooler_output[i]["hidden"], oh[j:j + 1], mean_tol=6e-3, what=f"{k} hidden")
+                assert_e2e_close(out.pooler_output[i]["hidden"], oh[j:j + 1], mean_tol=6e-3, what=f"{k} hidden", deferred_rstd=True)      # a decode step's qkv / gate_up (gemm.hip PRO 3)
             got = out.sampled_token_ids[i][0]
             check_token(k, got, int(oi[j]), ol[j], steps[j])
             force(k, int(oi[j]), oh[j], got)

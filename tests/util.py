@@ -37,21 +37,24 @@ def assert_f32_close(got: torch.Tensor, ref: torch.Tensor, *, atol: float = 1e-3
 
 # Round 6: the norm-fused GEMMs of the decode step (qkv, gate_up: launch path and chains alike) apply the row's rstd to the fp32 sums --
 # rstd * sum(W * bf16(w r)) -- instead of normalising every operand element first -- sum(W * bf16(w * bf16(r rstd))): one bf16 rounding
-# per element where the reference has two.  The HIP path is no longer a bit-faithful replay of the oracle's rounding points but a second
-# bf16 pipeline of the same accuracy (the three-way statement of tests/test_gpu_parity_full.py is the gate: HIP no farther from
-# fp32-activation arithmetic than the reference's own rounding is, x 1.3).  Against the bf16 oracle two such pipelines sit about one rounding
-# apart: every end-to-end bound has a floor of 0.75 ulp (mean) / + 2 ulps (max) at the tensor's scale; callers' tighter figures still
-# document what the bit-faithful arithmetic of rounds 1-5 measured.
+# per element where the reference has two.  Behind such a GEMM the HIP path is no longer a bit-faithful replay of the oracle's rounding points
+# but a second bf16 pipeline of the same accuracy (the three-way statements of tests/test_gpu_parity_full.py and
+# tests/test_gpu_predictor_accuracy.py are the gate: HIP no farther from fp32-activation arithmetic than the reference's own rounding is,
+# x 1.3).  Against the bf16 oracle two such pipelines sit about one rounding apart: a comparison that CROSSES a deferred GEMM -- the caller says
+# so with deferred_rstd=True, and DESIGN section 4 names the GEMM per call site -- has a floor of 0.75 ulp (mean) / + 2 ulps (max) at the
+# tensor's scale.  Every other comparison (prefill, MoE block, resize MLP, all-reduce, separate-norm paths, two schedules of one library,
+# the exact-rstd mode of the debug library) keeps the bounds the bit-faithful arithmetic of rounds 1-5 met.
 E2E_MEAN_FLOOR_ULPS = 0.75
 E2E_EXTRA_MAX_ULPS = 2.0
 
 
 def assert_e2e_close(got: torch.Tensor, ref: torch.Tensor, *, mean_tol: float = 4e-3, max_ulps: float = 2.0,
-                     what: str = "") -> None:
+                     what: str = "", deferred_rstd: bool = False) -> None:
     """End-to-end (multi-layer) comparison of bf16 activations / logits.  A 1-ulp rounding flip
     upstream moves every downstream value by an absolute amount, so the bound is stated at the
-    tensor's scale: max |diff| <= max_ulps (+ E2E_EXTRA_MAX_ULPS) bf16 ulps of the largest magnitude, mean |diff| <= mean_tol
-    (or E2E_MEAN_FLOOR_ULPS ulps at that scale, whichever is larger; see the note above and DESIGN.md 'Parity')."""
+    tensor's scale: max |diff| <= max_ulps bf16 ulps of the largest magnitude, mean |diff| <= mean_tol.
+    deferred_rstd=True (only where a deferred-rstd GEMM lies between the inputs and `got`, see the note above and DESIGN.md 'Parity'):
+    max_ulps + E2E_EXTRA_MAX_ULPS, and mean_tol no smaller than E2E_MEAN_FLOOR_ULPS ulps at that scale."""
     g, r = got.detach().float().cpu(), ref.detach().float().cpu()
     assert g.shape == r.shape, (what, g.shape, r.shape)
     fin = torch.isfinite(r)
@@ -59,8 +62,9 @@ def assert_e2e_close(got: torch.Tensor, ref: torch.Tensor, *, mean_tol: float = 
     d = (g[fin] - r[fin]).abs()
     amax = r[fin].abs().max().item()
     ulp = 2.0 ** (int(np.floor(np.log2(max(amax, 1e-30)))) - 7)
-    max_ulps = max_ulps + E2E_EXTRA_MAX_ULPS
-    mean_tol = max(mean_tol, E2E_MEAN_FLOOR_ULPS * ulp)
+    if deferred_rstd:
+        max_ulps = max_ulps + E2E_EXTRA_MAX_ULPS
+        mean_tol = max(mean_tol, E2E_MEAN_FLOOR_ULPS * ulp)
     assert d.max().item() <= (max_ulps + 0.02) * ulp, \
         f"{what}: max diff {d.max().item():.4g} > {max_ulps} ulp ({max_ulps * ulp:.4g}) at scale {amax:.3g}"
     assert d.mean().item() <= mean_tol, f"{what}: mean diff {d.mean().item():.4g} > {mean_tol:.4g}"
@@ -85,6 +89,19 @@ def codes_on_the_oracles_frame(got: torch.Tensor, ref: torch.Tensor, cp_logits: 
         assert float(top[0] - top[1]) <= tie, f"{what}: row {b}: code group {gfirst} differs without a near-tie (margin {float(top[0] - top[1]):.4g} > {tie:.4g})"
         on[b] = False
     return on
+
+
+def report_dir() -> str:
+    """The directory (relative to the working directory, created on demand) in which the parity tests leave their measured figures as
+    JSON, beside three_way_parity.json and the other reports of tests/test_gpu_parity_full.py: the run-output directory that .gitignore
+    keeps out of history (its one `*_out/` entry), so that a new report cannot land in a place that gets committed."""
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, ".gitignore")) as f:
+        outs = [ln.strip().rstrip("/") for ln in f if ln.strip().endswith("_out/")]
+    assert len(outs) == 1, f".gitignore must name exactly one run-output directory: {outs}"
+    os.makedirs(outs[0], exist_ok=True)
+    return outs[0]
 
 
 def make_moe_weights(H: int, E: int, I: int, Is: int, seed: int) -> dict:
