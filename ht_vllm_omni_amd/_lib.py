@@ -51,6 +51,19 @@ class TileGemm(C.Structure):
 TILE_ACT_NONE, TILE_ACT_GELU, TILE_ACT_SILU_MUL_GU8 = 0, 1, 2
 
 
+class MoeAlign(C.Structure):
+    """omni_moe_align_args: expert grouping of a prompt batch's (token, expert) slots on the device."""
+    _fields_ = [("topk_idx", vp), ("topk_w", vp), ("T", i32), ("top_k", i32), ("e0", i32), ("E_local", i32), ("block", i32), ("r_max", i32),
+                ("counts_ws", vp), ("row_start", vp), ("block_expert", vp), ("row_token", vp), ("row_weight", vp), ("slot_row", vp)]
+
+
+class MoePrefill(C.Structure):
+    """omni_moe_prefill_args: the expert GEMMs and the combine over the maps of omni_moe_align."""
+    _fields_ = [("x", vp), ("topk_idx", vp), ("T", i32), ("H", i32), ("I", i32), ("top_k", i32), ("E_local", i32), ("block", i32), ("r_max", i32),
+                ("block_expert", vp), ("row_token", vp), ("row_weight", vp), ("slot_row", vp), ("w_gate_up", vp), ("w_down", vp),
+                ("gu_ws", vp), ("act_ws", vp), ("y_ws", vp), ("shared", vp), ("gate_logit", vp), ("ld_gate", i32), ("out", vp)]
+
+
 class ResUnit(C.Structure):
     """omni_res_unit (include/omni_codec.h): one fused residual unit of the Code2Wav decoder."""
     _fields_ = [("s", vp), ("h", vp), ("s_next", vp), ("w1", vp), ("b1", vp), ("snake2_alpha", vp), ("snake2_inv_beta", vp),
@@ -111,6 +124,8 @@ SIGNATURES = {
     "omni_moe_experts_resid": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "omni_snake_beta": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "omni_gemm_tile": (i32, [C.POINTER(TileGemm), vp]),
+    "omni_moe_align": (i32, [C.POINTER(MoeAlign), vp]),
+    "omni_moe_prefill_experts": (i32, [C.POINTER(MoePrefill), vp]),
     # include/omni_codec.h
     "omni_codec_rvq_embed": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp]),
     "omni_codec_rmsnorm": (i32, [vp, i32, vp, f32, vp, i32, i32, vp]),

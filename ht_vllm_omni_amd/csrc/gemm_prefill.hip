@@ -25,6 +25,7 @@
 // Workgroups are dealt to the 8 XCDs in contiguous chunks of the (n block, m block) order, m fastest: the workgroups that
 // share an L2 share a W panel.
 #include "common.cuh"
+#include "gemm_frag.cuh"
 #include "kernels.h"
 
 #define TG_WAVES 8
@@ -32,7 +33,6 @@
 #define TG_OOB 0x80000000u           // byte offset beyond any descriptor (num_records < 2^31): reads as zero
 #define TG_LDS_MAX (160 * 1024)
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 struct TileArgs {
@@ -51,6 +51,10 @@ struct TileArgs {
     // tiles past it leave at once, rows past it read as zero and are not stored
     long long gx_rows, gw_elems, gout_rows;
     const int32_t* group_rows;
+    // MoE prefill over the expert-sorted compact batch (moe_prefill.hip, MOE != 0 instantiations): m block b belongs to expert
+    // block_expert[b] (< 0: no rows, the workgroup leaves) and reads W + expert * gw_elems; batch row r is token row row_token[r] of x
+    // (< 0: a padding row, reads as zero) and carries the routing weight row_weight[r] (bf16)
+    const int32_t* block_expert; const int32_t* row_token; const uint16_t* row_weight;
 };
 
 __device__ __forceinline__ f32x4 tg_mfma(u32x4 a, u32x4 b, f32x4 c) {
@@ -225,7 +229,14 @@ struct TileGeom {
     static_assert(WN % 2 == 0 && LDS_BYTES <= TG_LDS_MAX, "geometry");
 };
 
-template <int WAVES_N, int WN, int WM, bool GU8>
+// MOE != 0: the same staging, ring and slice order over the MoE prefill's compact batch (one m block = BM rows of ONE expert):
+//   MOE_GU_FUSED  x rows gathered through row_token; W = the decode step's [gate rows | up rows] matrix (a.N = 2 I rows): n block nb covers
+//                 columns [nb BN/2, + BN/2) of gate AND of up, the first WN/2 n-tiles of a wave being gate and the second WN/2 the SAME columns
+//                 of up -- gate and up of an output element meet in one lane, SiLU(gate) * up runs in registers, out = act [rows, I];
+//   MOE_GU_PLAIN  x gathered, plain [rows, 2 I] output (widths the fused arrangement does not divide; omni_silu_mul follows);
+//   MOE_DOWN      x = act rows as they lie, out = bf16(bf16(acc) * row_weight[row]).
+// (the mode numbers: kernels.h)
+template <int WAVES_N, int WN, int WM, bool GU8, int MOE = 0>
 __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_in) {
     using G = TileGeom<WAVES_N, WN, WM>;
     TileArgs a = a_in;
@@ -270,6 +281,11 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
     }
     const int m0 = m_blk * G::BM, n0 = n_blk * G::BN;
     if (m0 >= a.M) return;                                                    // a group with fewer rows than the launch's M (uniform)
+    if constexpr (MOE != 0) {
+        const int expert = a.block_expert[m_blk];                             // uniform: one expert per m block
+        if (expert < 0) return;                                               // past the last expert's rows
+        a.W += (size_t)expert * a.gw_elems;
+    }
     const int nsteps = a.K >> 5;                                              // 32-deep slices
 
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (int)((size_t)a.N * a.K * 2), 0x00020000);
@@ -282,13 +298,23 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
 #pragma unroll
     for (int i = 0; i < NLW; ++i) {
         const int f = wave + TG_WAVES * i;
-        const int n16 = (n0 >> 4) + f;
-        wbase[i] = (f < NTILES && n16 * 16 < a.N) ? (unsigned)((size_t)n16 * nsteps * 1024 + lane * 16) : TG_OOB;
+        int n16 = (n0 >> 4) + f;
+        bool in_n = n16 * 16 < a.N;
+        if constexpr (MOE == MOE_GU_FUSED) {                                  // tile f = n-tile j of wave column f / WN: gate (j < WN / 2) or up
+            constexpr int HN = WN / 2;
+            const int j = f % WN;
+            const int col16 = n_blk * (NTILES / 2) + (f / WN) * HN + j % HN;  // 16-column tile of the [rows, I] output
+            in_n = col16 * 32 < a.N;
+            n16 = (j >= HN ? a.N >> 5 : 0) + col16;
+        }
+        wbase[i] = (f < NTILES && in_n) ? (unsigned)((size_t)n16 * nsteps * 1024 + lane * 16) : TG_OOB;
     }
 #pragma unroll
     for (int i = 0; i < NLX; ++i) {
         const int g = wave + TG_WAVES * i;
         xrow[i] = (int)x_lo + m0 + g * 16 + c + a.row_off;
+        if constexpr (MOE == MOE_GU_FUSED || MOE == MOE_GU_PLAIN)             // the gather: the lane's source row is the batch row's token
+            xrow[i] = g < G::MTILES ? a.row_token[m0 + g * 16 + c] : -1;
         xbyte[i] = (xrow[i] * a.ldx + 8 * q) * 2;        // wraps out of the descriptor for rows < 0 (never used then)
     }
     int seg = 0, cs = 0;                                  // segment walk of the NEXT slice to stage: k = seg * seg_len + cs
@@ -369,8 +395,34 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
 #undef TG_SLICE
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is dead: its tail loads (zeros) landed
 
-    if (tile_plain(a)) tile_epilogue<WN, WM, GU8, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
-    else tile_epilogue<WN, WM, GU8, false>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
+    if constexpr (MOE == MOE_GU_FUSED) {
+        constexpr int HN = WN / 2;
+        f32x4 o[HN][WM];
+#pragma unroll
+        for (int j = 0; j < HN; ++j)
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[j][i][e] = silu_mul_bf16(acc[j][i][e], acc[HN + j][i][e]);
+        a.N >>= 1;                                                            // the output's width
+        tile_epilogue<HN, WM, false, true>(a, o, lds, wave, lane, m0 + wm * WM * 16, n_blk * (G::BN / 2) + wn * HN * 16);
+    } else if constexpr (MOE == MOE_DOWN) {
+        // the two rounding points of y = bf16(acc) followed by y * weight on bf16 tensors; the lane holds row (lane & 15) of m-tile i
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+            const float wgt = bf2f(a.row_weight[m0 + (wm * WM + i) * 16 + c]);
+#pragma unroll
+            for (int j = 0; j < WN; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[j][i][e] = bfround(acc[j][i][e]) * wgt;
+        }
+        tile_epilogue<WN, WM, false, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
+    } else if constexpr (MOE == MOE_GU_PLAIN) {
+        tile_epilogue<WN, WM, false, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
+    } else {
+        if (tile_plain(a)) tile_epilogue<WN, WM, GU8, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
+        else tile_epilogue<WN, WM, GU8, false>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
+    }
 }
 
 // ---- the two-group ("ping-pong") form of the 256-column tile.  Same images, same MFMA, same accumulation order as gemm_tile_kernel
@@ -706,4 +758,60 @@ extern "C" int omni_gemm_tile(const omni_tile_gemm* g, void* stream) {
     if (N % 128 == 0) return launch_tile<1, 8, 4, false>(a, st, groups);
     if (N % 96 == 0) return launch_tile<1, 6, 4, false>(a, st, groups);
     return N > 128 ? launch_tile<2, 8, 4, false>(a, st, groups) : launch_tile<1, 8, 4, false>(a, st, groups);
+}
+
+// ---- the MoE prefill's expert GEMMs over the compact batch (entry points: moe_prefill.hip).  Two block heights with the K-slice order of
+// every other geometry (bit-identical expert outputs): 64 rows = <4, 2, 2> (128 columns; fused: 64 gate + 64 up), 256 rows = <2, 8, 4>
+// (256 columns; fused: 128 + 128).
+template <int WAVES_N, int WN, int WM, int MOE>
+static int launch_tile_moe(TileArgs a, hipStream_t st) {
+    using G = TileGeom<WAVES_N, WN, WM>;
+    a.mblocks = a.M / G::BM;
+    a.nblocks = MOE == MOE_GU_FUSED ? (a.N / 2) / (G::BN / 2) : (a.N + G::BN - 1) / G::BN;
+    {
+        const int per_xcd = (a.mblocks * a.nblocks + 7) / 8;
+        int band = 1;
+        while (band * band < per_xcd) ++band;
+        a.band = band > a.mblocks ? a.mblocks : band;
+    }
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_kernel<WAVES_N, WN, WM, false, MOE>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+        if (e != hipSuccess) { omni_set_error("omni_moe_prefill_experts: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_tile_kernel<WAVES_N, WN, WM, false, MOE>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), G::LDS_BYTES, st, a);
+    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts");
+    return OMNI_OK;
+}
+
+bool k_moe_tile_fused_ok(int block, int I) { return I % (block == 64 ? 64 : 128) == 0; }
+
+int k_moe_tile_gemm(int mode, int block, const void* x, int64_t x_rows, int ldx, const void* w, int64_t w_expert_elems, int experts,
+                    const int32_t* block_expert, const int32_t* row_token, const void* row_weight, void* out, int ldo, int rows, int N, int K,
+                    void* stream) {
+    OMNI_CHECK_ARG(x && w && block_expert && out && (mode == MOE_DOWN ? row_weight != nullptr : row_token != nullptr), "omni_moe_prefill_experts: null argument");
+    OMNI_CHECK_ARG((block == 64 || block == 256) && rows > 0 && rows % block == 0, "omni_moe_prefill_experts: block=%d rows=%d", block, rows);
+    OMNI_CHECK_ARG(N > 0 && N % 16 == 0 && K > 0 && K % 32 == 0 && ldx % 8 == 0 && ldx >= K && ldo % 8 == 0, "omni_moe_prefill_experts: N=%d K=%d ldx=%d ldo=%d", N, K, ldx, ldo);
+    OMNI_CHECK_ARG(x_rows > 0 && x_rows * (int64_t)ldx * 2 < (int64_t)TG_OOB && (int64_t)N * K * 2 < (int64_t)TG_OOB, "omni_moe_prefill_experts: an operand exceeds the 2 GB descriptor");
+    OMNI_CHECK_ARG(mode != MOE_DOWN || x_rows >= rows, "omni_moe_prefill_experts: act rows");
+    OMNI_CHECK_ARG(mode != MOE_GU_FUSED || (N % 32 == 0 && k_moe_tile_fused_ok(block, N / 2)), "omni_moe_prefill_experts: the fused gate_up tile needs I %% %d == 0", block == 64 ? 64 : 128);
+    OMNI_CHECK_ARG(experts >= 1 && w_expert_elems >= (int64_t)N * K, "omni_moe_prefill_experts: expert stride");
+    TileArgs a{};
+    a.x = (const uint16_t*)x; a.x_rows = x_rows; a.ldx = ldx;
+    a.seg_len = K; a.seg_rows = 0; a.row_off = 0;
+    a.W = (const uint16_t*)w; a.gw_elems = w_expert_elems;
+    a.out = (uint16_t*)out; a.ldo = ldo;
+    a.M = rows; a.N = N; a.K = K; a.act = OMNI_TILE_ACT_NONE;
+    a.block_expert = block_expert; a.row_token = row_token; a.row_weight = (const uint16_t*)row_weight;
+    hipStream_t st = (hipStream_t)stream;
+    if (block == 64) {
+        if (mode == MOE_GU_FUSED) return launch_tile_moe<4, 2, 2, MOE_GU_FUSED>(a, st);
+        if (mode == MOE_GU_PLAIN) return launch_tile_moe<4, 2, 2, MOE_GU_PLAIN>(a, st);
+        return launch_tile_moe<4, 2, 2, MOE_DOWN>(a, st);
+    }
+    if (mode == MOE_GU_FUSED) return launch_tile_moe<2, 8, 4, MOE_GU_FUSED>(a, st);
+    if (mode == MOE_GU_PLAIN) return launch_tile_moe<2, 8, 4, MOE_GU_PLAIN>(a, st);
+    return launch_tile_moe<2, 8, 4, MOE_DOWN>(a, st);
 }

@@ -145,7 +145,7 @@ class TalkerEngine:
                  block_size: int = 16, max_batch: int = 64, device: str = "cuda:0", tp_rank: int = 0, tp_size: int = 1,
                  k_scale: float = 1.0, v_scale: float = 1.0, allow_eos: bool = True, masked_logit: float = 0.0, tp_group=None, n_sub: int = 1, tp_force: bool = False, frag_layout: bool = True,
                  fused_norm: bool | None = None, peer_allreduce=None, moe_fp8: bool = False, prefill_gemm: str = "tile",
-                 calculate_kv_scales: bool = False):
+                 calculate_kv_scales: bool = False, moe_dispatch: str = "device"):
         if not torch.cuda.is_available():
             raise L.OmniError("TalkerEngine needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
         self.lib = L.load()
@@ -163,6 +163,13 @@ class TalkerEngine:
         if prefill_gemm not in ("tile", "blas", "both"):
             raise ValueError(f"prefill_gemm={prefill_gemm!r}")
         self.prefill_gemm = prefill_gemm if self.frag_layout else "blas"
+        # MoE prefill on the tile kernel: "device" = expert grouping on the device, gathered / fused expert GEMMs over the compact batch
+        # (ops.moe_prefill_experts: no host read per layer); "padded" = the earlier torch grouping into a padded [E, cap, H] batch (one
+        # host read per layer), kept for A/B -- same expert arithmetic, bit-identical routed-expert outputs
+        if moe_dispatch not in ("device", "padded"):
+            raise ValueError(f"moe_dispatch={moe_dispatch!r}")
+        self.moe_dispatch = moe_dispatch
+        self.moe_block: int | None = None       # A/B: force the device dispatch's block height (64 | 256); None = ops.moe_block_height
         # norm-free residual stream (omni_gemm_resid / omni_gemm_xnorm; MoE layers: omni_moe_experts_resid): single rank, or
         # tensor- / expert-parallel ranks with the peer-mapped all-reduce (it sums the partials BEFORE the residual add);
         # ranks that all-reduce through RCCL between the phase calls keep the separate norms
@@ -751,16 +758,28 @@ class TalkerEngine:
             out += ys[:, j]
         return out
 
-    def _moe_mlp_tile(self, a: torch.Tensor, w: dict) -> torch.Tensor:
-        """Sparse-MoE MLP over T prompt rows on the hand-written MFMA kernel: router, both expert GEMMs (ONE grouped
-        omni_gemm_tile launch each over the expert-sorted [E, cap, H] batch, reading the decode step's fragment-major expert
-        matrices; tiles past an expert's live rows leave at once) and the shared expert -- no library GEMM on the path.
-        Same grouping, rounding points and accumulation order as _moe_mlp_blas (reference: vLLM FusedMoE under
-        V/model_executor/models/qwen3_omni/qwen3_moe.py:8,152-161; arithmetic = HF's expert loop, oracle.moe_block)."""
+    def _moe_mlp_tile(self, a: torch.Tensor, w: dict, shared_term: bool = True) -> torch.Tensor:
+        """Sparse-MoE MLP over T prompt rows on the hand-written MFMA kernel: router, both expert GEMMs and the shared expert -- no
+        library GEMM on the path.  moe_dispatch "device" (default): the slots are grouped on the device into a compact expert-sorted
+        batch, the gate_up GEMM gathers its rows from `a` and applies SiLU * up in its epilogue, the down GEMM applies the routing
+        weight, one kernel combines (ops.moe_prefill_experts; expert-parallel ranks pass their window, foreign slots take no rows):
+        nothing reads device data on the host.  "padded": ONE grouped omni_gemm_tile launch per GEMM over the expert-sorted padded
+        [E, cap, H] batch built with torch ops (tiles past an expert's live rows leave at once; cap is read on the host).
+        Same grouping order, rounding points and accumulation order in both and in _moe_mlp_blas (reference: vLLM FusedMoE under
+        V/model_executor/models/qwen3_omni/qwen3_moe.py:8,152-161; arithmetic = HF's expert loop, oracle.moe_block).
+        shared_term=False leaves the shared expert's term out (tests: the routed experts alone)."""
         d = self.d
         T, H = a.shape
         E, k, I = self.moe_experts_l, d.moe_top_k, self.moe_inter_l
         idx, wts = ops.moe_route(ops.gemm_tile(a, w["moe_router_f"]), k, d.moe_norm_topk)      # int32 [T, k], bf16 [T, k]
+        with_shared = shared_term and self.moe_shared_l > 0
+        if self.moe_dispatch == "device":
+            sh = gate = None
+            if with_shared:
+                sh = ops.gemm_tile(ops.silu_mul(ops.gemm_tile(a, w["moe_shared_gate_up_f"])), w["moe_shared_down_f"])
+                gate = ops.gemm_tile(a, w["moe_shared_gate_f"])
+            return ops.moe_prefill_experts(a, idx, wts, w["moe_gate_up_f"], w["moe_down_f"], E=d.moe_experts, e0=self.moe_e0, shared=sh,
+                                           gate_logit=gate, block=self.moe_block)
         order, dst, wts_s, counts, cap = self._moe_group_slots(idx, wts, T)
         rows = counts.to(torch.int32)
         xb = torch.empty(E * cap, H, dtype=BF16, device=a.device)       # rows past an expert's count are never read
@@ -769,7 +788,7 @@ class TalkerEngine:
         act = ops.silu_mul(gu)
         y = ops.gemm_tile(act, w["moe_down_f"], groups=E, group_rows=rows)                      # [E * cap, H]
         out = self._moe_combine(y, order, dst, wts_s, T)
-        if self.moe_shared_l > 0:
+        if with_shared:
             sh = ops.gemm_tile(ops.silu_mul(ops.gemm_tile(a, w["moe_shared_gate_up_f"])), w["moe_shared_down_f"])
             gate = ops.gemm_tile(a, w["moe_shared_gate_f"])[:, :1]
             out = out + torch.sigmoid(gate) * sh

@@ -109,6 +109,105 @@ def moe_block(x, w, top_k, norm_topk_prob=False):
     return out, idx, wts
 
 
+MOE_BLOCK_SMALL, MOE_BLOCK_BIG = 64, 256
+# mean rows per expert from which the 256-row block is taken (below it: 64 rows).  Known from T, k and E alone -- no device read.
+MOE_BLOCK_THRESHOLD = 128
+
+
+def moe_block_height(T: int, top_k: int, n_local: int) -> int:
+    return MOE_BLOCK_SMALL if T * top_k < MOE_BLOCK_THRESHOLD * n_local else MOE_BLOCK_BIG
+
+
+def moe_r_max(T: int, top_k: int, n_local: int, block: int) -> int:
+    """Rows of the compact expert-sorted batch: every expert may waste block - 1 rows, whatever the routing."""
+    return (T * top_k + n_local * (block - 1) + block - 1) // block * block
+
+
+def moe_align(idx, wts, E, block=64, e0=0, n_local=None):
+    """omni_moe_align: the slots of topk_idx int32 [T, k] (weights bf16 [T, k]) grouped by expert, every expert of the window
+    [e0, e0 + n_local) starting on a multiple of `block` rows; all on the device, all sizes from (T, k, n_local, block).
+    Returns (row_start int32 [n_local + 1], block_expert int32 [r_max / block], row_token int32 [r_max], row_weight bf16 [r_max],
+    slot_row int32 [T * k])."""
+    _chk_dev(idx, wts)
+    T, k = idx.shape
+    n_local = E if n_local is None else n_local
+    if idx.dtype != torch.int32 or wts.dtype != BF16 or wts.shape != idx.shape or e0 < 0 or e0 + n_local > E:
+        raise L.OmniError("moe_align: idx int32 [T, k], wts bf16 [T, k], window inside [0, E)")
+    r_max = moe_r_max(T, k, n_local, block)
+    dev = idx.device
+    ints = torch.empty(9 * n_local + 1 + r_max // block + r_max + T * k, dtype=torch.int32, device=dev)      # one allocation for the int maps
+    counts, row_start, block_expert, row_token, slot_row = torch.split(ints, [8 * n_local, n_local + 1, r_max // block, r_max, T * k])
+    row_weight = torch.empty(r_max, dtype=BF16, device=dev)
+    g = L.MoeAlign()
+    g.topk_idx, g.topk_w = idx.data_ptr(), wts.data_ptr()
+    g.T, g.top_k, g.e0, g.E_local, g.block, g.r_max = T, k, e0, n_local, block, r_max
+    g.counts_ws, g.row_start, g.block_expert = counts.data_ptr(), row_start.data_ptr(), block_expert.data_ptr()
+    g.row_token, g.row_weight, g.slot_row = row_token.data_ptr(), row_weight.data_ptr(), slot_row.data_ptr()
+    L.check(L.load().omni_moe_align(C.byref(g), L.current_stream()), "omni_moe_align")
+    return row_start, block_expert, row_token, row_weight, slot_row
+
+
+def moe_prefill_experts(x, idx, wts, gate_up_f, down_f, *, E, e0=0, shared=None, gate_logit=None, block=None):
+    """Routed experts + combine of the sparse-MoE MLP over T >= 1 rows with no host read (omni_moe_align + omni_moe_prefill_experts):
+    x bf16 [T, H], routing idx / wts [T, k] over E experts, gate_up_f [n_local, 2I, H] / down_f [n_local, H, I] fragment-major per
+    expert = experts [e0, e0 + n_local); shared bf16 [T, H] + gate_logit bf16 [T, >= 1] (column 0): the sigmoid-gated shared expert's
+    term.  block: 64 | 256 rows per expert block (None: from the mean rows per expert).  Scratch comes from torch's allocator (a captured
+    graph owns it).  Returns bf16 [T, H]."""
+    _chk_dev(x, idx, wts, gate_up_f, down_f, shared)
+    T, H = x.shape
+    k = idx.shape[1]
+    n_local, two_i = gate_up_f.shape[0], gate_up_f.shape[1]
+    I = two_i // 2
+    block = moe_block_height(T, k, n_local) if block is None else block
+    row_start, block_expert, row_token, row_weight, slot_row = moe_align(idx, wts, E, block, e0, n_local)
+    r_max = row_token.numel()
+    dev = x.device
+    g = L.MoePrefill()
+    g.x, g.topk_idx = x.data_ptr(), idx.data_ptr()
+    g.T, g.H, g.I, g.top_k, g.E_local, g.block, g.r_max = T, H, I, k, n_local, block, r_max
+    g.block_expert, g.row_token, g.row_weight, g.slot_row = block_expert.data_ptr(), row_token.data_ptr(), row_weight.data_ptr(), slot_row.data_ptr()
+    g.w_gate_up, g.w_down = gate_up_f.data_ptr(), down_f.data_ptr()
+    act = torch.empty(r_max, I, dtype=BF16, device=dev)
+    y = torch.empty(r_max, H, dtype=BF16, device=dev)
+    gu = torch.empty(r_max, two_i, dtype=BF16, device=dev) if I % (64 if block == 64 else 128) else None      # widths the fused epilogue does not divide
+    out = torch.empty(T, H, dtype=BF16, device=dev)
+    g.gu_ws, g.act_ws, g.y_ws, g.out = L.ptr(gu), act.data_ptr(), y.data_ptr(), out.data_ptr()
+    if shared is not None:
+        if gate_logit is None or gate_logit.dtype != BF16 or gate_logit.stride(1) != 1 or gate_logit.shape[0] != T or not gate_logit.is_cuda:
+            raise L.OmniError("moe_prefill_experts: shared needs gate_logit bf16 [T, >= 1]")
+        g.shared, g.gate_logit, g.ld_gate = shared.data_ptr(), gate_logit.data_ptr(), gate_logit.stride(0)
+    L.check(L.load().omni_moe_prefill_experts(C.byref(g), L.current_stream()), "omni_moe_prefill_experts")
+    return out
+
+
+def _frag(w):
+    """[N, K] row-major -> fragment-major on the device (engine.frag_shuffle; N padded to whole 16-row tiles)."""
+    N, K = w.shape
+    if N % 16:
+        w = torch.cat([w, torch.zeros(16 - N % 16, K, dtype=w.dtype, device=w.device)])
+    return w.reshape(-1, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(-1, K)
+
+
+def moe_block_prefill(x, w, top_k, norm_topk_prob=False, block=None):
+    """moe_block for any T >= 1 (the decode op stops at 64 rows): router, routed experts and shared expert on the tile kernel, expert
+    grouping on the device -- no host read, capturable in a graph.  Same weight dict as moe_block; the row-major router / shared-expert
+    matrices are brought to fragment-major here unless the dict already holds them as router_f, shared_gate_up_f, shared_down_f,
+    shared_gate_f ([16, H]: the gate's row padded to one tile).  Returns (out bf16 [T, H], idx, wts)."""
+    E = w["gate_up_f"].shape[0]
+    f = lambda n: w[n + "_f"] if w.get(n + "_f") is not None else _frag(w[n])      # noqa: E731
+    logits = gemm_tile(x, f("router"))
+    if logits.shape[1] != E:        # a router of fewer rows than a tile was padded: the padding columns are no experts
+        logits = logits[:, :E].contiguous()
+    idx, wts = moe_route(logits, top_k, norm_topk_prob)
+    shared = gate = None
+    sgu = w.get("shared_gate_up_f") if w.get("shared_gate_up_f") is not None else w.get("shared_gate_up")
+    if sgu is not None and sgu.shape[0] > 0:
+        shared = gemm_tile(silu_mul(gemm_tile(x, f("shared_gate_up"))), f("shared_down"))
+        gate = gemm_tile(x, f("shared_gate"))
+    out = moe_prefill_experts(x, idx, wts, w["gate_up_f"], w["down_f"], E=E, shared=shared, gate_logit=gate, block=block)
+    return out, idx, wts
+
+
 def snake_beta(x, exp_alpha, inv_beta):
     """SnakeBeta of the Code2Wav decoder: x [B, C, T] fp32 or bf16 -> x + inv_beta[c] * sin(x * exp_alpha[c])^2."""
     _chk_dev(x, exp_alpha, inv_beta)

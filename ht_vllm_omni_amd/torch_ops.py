@@ -13,6 +13,8 @@ has kernels: a CPU tensor fails loudly with PyTorch's "no kernel for backend" er
   qknorm_rope_kvwrite_(qkv, qnorm_w, knorm_w, positions, cos_sin, slots, q_out, k_cache, v_cache, ...)   q/k-norm + RoPE + cache write
   paged_attn_decode(q, k_cache, v_cache, block_table, seq_lens, ...) -> Tensor      vLLM paged attention, query_len 1
   paged_attn_prefill(q, k_cache, v_cache, block_table, req_of_tok, positions, ...) -> Tensor
+  moe_block_prefill(x, router, gate_up_f, down_f, shared_gate_up?, shared_down?, shared_gate?, top_k, norm_topk_prob, block)
+        -> (out, topk_idx, topk_w)                                      FusedMoE for prompt rows (any T; no host read, graph-safe)
   topk_sample(logits, seen?, steps?, greedy, temperature, top_k, top_p, rep_penalty, seed, ...) -> Tensor   vLLM Sampler
   allreduce_oneshot_(peers, r_io?, partials?, out?, which, M)          RowParallelLinear's all-reduce (tp_comm.PeerAllReduce)
   decode_step_(engine, out_record, positions, seq_lens, seen, steps, kv_caches, text_step, block_table, num_live, B, advance)
@@ -46,6 +48,8 @@ _lib.define("paged_attn_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor 
 _lib.define("paged_attn_prefill(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_table, Tensor req_of_tok, Tensor positions, "
             "Tensor? k_scales, Tensor? v_scales, int q_heads, int kv_heads, int head_dim, int block_size, int kv_dtype, float k_scale, "
             "float v_scale) -> Tensor")
+_lib.define("moe_block_prefill(Tensor x, Tensor router, Tensor gate_up_f, Tensor down_f, Tensor? shared_gate_up, Tensor? shared_down, "
+            "Tensor? shared_gate, int top_k, bool norm_topk_prob, int block) -> (Tensor, Tensor, Tensor)")
 _lib.define("topk_sample(Tensor logits, Tensor(a!)? seen, Tensor(b!)? steps, bool greedy, float temperature, int top_k, float top_p, "
             "float rep_penalty, int seed, int step_mul, int step_add, bool inc_steps) -> Tensor")
 _lib.define("allreduce_oneshot_(int peers, Tensor(a!)? r_io, Tensor(b!)? partials, Tensor(c!)? out, int which, int M, bool accumulate) -> ()")
@@ -111,6 +115,13 @@ def _paged_attn_prefill(q, k_cache, v_cache, block_table, req_of_tok, positions,
                                   v_scale=v_scale, k_scales=k_scales, v_scales=v_scales)
 
 
+@_impl("moe_block_prefill")
+def _moe_block_prefill(x, router, gate_up_f, down_f, shared_gate_up, shared_down, shared_gate, top_k, norm_topk_prob, block):
+    w = {"router": router, "gate_up_f": gate_up_f, "down_f": down_f, "shared_gate_up": shared_gate_up, "shared_down": shared_down,
+         "shared_gate": shared_gate}
+    return ops.moe_block_prefill(x, w, int(top_k), bool(norm_topk_prob), block=int(block) or None)      # block 0: chosen from T k / E
+
+
 @_impl("topk_sample")
 def _topk_sample(logits, seen, steps, greedy, temperature, top_k, top_p, rep_penalty, seed, step_mul, step_add, inc_steps):
     return ops.sample(logits, greedy=bool(greedy), temperature=temperature, top_k=int(top_k), top_p=top_p, rep_penalty=rep_penalty,
@@ -158,4 +169,4 @@ def register_peers(ar) -> int:
 
 
 OPS = ("rmsnorm_residual_", "skinny_gemm", "silu_mul", "lmhead_mask", "qknorm_rope_kvwrite_", "paged_attn_decode", "paged_attn_prefill",
-       "topk_sample", "allreduce_oneshot_", "decode_step_")
+       "moe_block_prefill", "topk_sample", "allreduce_oneshot_", "decode_step_")

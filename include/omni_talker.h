@@ -178,6 +178,49 @@ typedef struct omni_tile_gemm {
 } omni_tile_gemm;
 int omni_gemm_tile(const omni_tile_gemm* g, void* stream);
 
+/* Sparse-MoE MLP over T >= 1 prompt rows with NO host read between the router and the block's output (csrc/moe_prefill.hip; the
+ * expert GEMMs are instantiations of the tile kernel above).  Replaces the batched expert GEMMs vLLM's FusedMoE issues for prompt
+ * tokens (V/model_executor/models/qwen3_omni/qwen3_moe.py:8,152-161); arithmetic and rounding points = omni_moe_experts.
+ *
+ * omni_moe_align: the (token, expert) slots of topk_idx int32 [T, k] grouped by expert into a compact batch whose experts start on
+ * multiples of `block` (64 | 256) rows; experts outside the window [e0, e0 + E_local) take no rows.  Every size depends on
+ * (T, k, E_local, block) alone: r_max = T k + E_local (block - 1) rounded up to `block`.  Inside an expert the rows are in
+ * ascending slot (= token) order -- deterministic, no atomics.
+ *   row_start    int32 [E_local + 1]   first batch row of each expert; [E_local] = rows in use
+ *   block_expert int32 [r_max / block] expert (local number) that owns each block, -1 past the end
+ *   row_token    int32 [r_max]         source token of each batch row, -1 for padding rows
+ *   row_weight   bf16  [r_max]         topk_w of that slot (0 for padding rows)
+ *   slot_row     int32 [T k]           batch row of slot (t, j), -1 when its expert is outside the window
+ *   counts_ws    int32 [8 E_local]     scratch                                                                               */
+typedef struct omni_moe_align_args {
+    const int32_t* topk_idx; const void* topk_w;
+    int T, top_k, e0, E_local, block, r_max;
+    int32_t* counts_ws;
+    int32_t* row_start; int32_t* block_expert; int32_t* row_token; void* row_weight; int32_t* slot_row;
+} omni_moe_align_args;
+int omni_moe_align(const omni_moe_align_args* a, void* stream);
+
+/* omni_moe_prefill_experts: over the maps of omni_moe_align (same block, r_max):
+ *   act [r_max, I] = SiLU(x_tok . Wg_e^T) * (x_tok . Wu_e^T)   x bf16 [T, H] read THROUGH row_token (no gathered copy); fused into the
+ *                    gate_up tile's epilogue when I % 64 == 0 (block 64) / I % 128 == 0 (block 256), else through gu_ws bf16
+ *                    [r_max, 2 I] (then required) + omni_silu_mul's kernel;
+ *   y [r_max, H]   = bf16(bf16(act . Wd_e^T) * row_weight)
+ *   out [T, H]     = per token the sum of its k rows of y in ascending expert index, bf16 accumulate, slots with slot_row < 0 as zero,
+ *                    + bf16(bf16(sigmoid(gate_logit[t])) * shared[t]) when shared != NULL (gate_logit bf16, row stride ld_gate:
+ *                    column 0 of the shared-gate GEMM; shared bf16 [T, H]).
+ * w_gate_up bf16 [E_local, 2I, H] = [gate rows | up rows], w_down bf16 [E_local, H, I], each expert matrix fragment-major.
+ * H % 64 == 0, I % 32 == 0, top_k <= 8.                                                                                        */
+typedef struct omni_moe_prefill_args {
+    const void* x; const int32_t* topk_idx;
+    int T, H, I, top_k, E_local, block, r_max;
+    const int32_t* block_expert; const int32_t* row_token; const void* row_weight; const int32_t* slot_row;
+    const void* w_gate_up; const void* w_down;
+    void* gu_ws; void* act_ws; void* y_ws;
+    const void* shared; const void* gate_logit; int ld_gate;
+    void* out;
+} omni_moe_prefill_args;
+int omni_moe_prefill_experts(const omni_moe_prefill_args* a, void* stream);
+
 /* SnakeBeta activation of the Code2Wav decoder (next stage after the talker):
  *   out[b, c, t] = x + inv_beta[c] * sin^2(x * exp_alpha[c]),  x / out [B, C, T] contiguous fp32 (is_bf16 = 0) or bf16,
  *   exp_alpha = exp(alpha), inv_beta = 1 / (exp(beta) + 1e-9) fp32 [C].
