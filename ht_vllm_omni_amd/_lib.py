@@ -35,6 +35,11 @@ class LayerWeights(C.Structure):
                                   "moe_down_scale")]
 
 
+class DenseW8Layer(C.Structure):
+    """omni_dense_w8_layer: fp8 bytes (W8 fragment layout) + fp32 row scales of one backbone layer's four GEMMs."""
+    _fields_ = [(n, vp) for n in ("wqkv", "wo", "wgu", "wdown", "wqkv_scale", "wo_scale", "wgu_scale", "wdown_scale")]
+
+
 class ArPeers(C.Structure):
     """omni_ar_peers: peer-mapped partial buffers + flag words of a tensor-parallel group."""
     _fields_ = [("world", i32), ("rank", i32), ("data", vp * 8), ("flags", vp * 8), ("epoch", vp), ("error", vp), ("tile_flags", vp * 8)]
@@ -137,6 +142,10 @@ SIGNATURES = {
     "omni_codec_res_unit": (i32, [C.POINTER(ResUnit), vp]),
     "omni_gemm_resid": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
     "omni_gemm_xnorm": (i32, [vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
+    "omni_gemm_w8": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "omni_gemm_resid_w8": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
+    "omni_gemm_xnorm_w8": (i32, [vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "omni_talker_set_dense_w8": (i32, [vp, C.POINTER(DenseW8Layer)]),
     "omni_attn_decode_fused": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
                                      f32, f32, f32, i32, vp]),
     "omni_qknorm_rope_kvwrite": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, f32, f32, vp]),

@@ -123,6 +123,7 @@ struct omni_talker {
     int ran;                            // persistent chains launched by the decode-step call in progress / last made (bit 0 cp, bit 1 bb)
     bool head_fused = false;            // the last backbone launch of the step in progress computed logits + h[t + 1] (run_backbone fuse_head)
     bool tail_fused = false;            // the predictor's all-pass launch of the step in progress assembled the backbone's input and computed layer 0's qkv
+    std::vector<omni_dense_w8_layer> w8;   // omni_talker_set_dense_w8: fp8 bytes + row scales of the backbone's four GEMMs per layer (empty: off)
 };
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -357,6 +358,31 @@ extern "C" int omni_talker_set_chains(omni_talker* t, int on) {
     return OMNI_OK;
 }
 extern "C" int omni_talker_chains_ran(const omni_talker* t) { return t ? t->ran : 0; }
+// Dense backbone decode on fp8 weights (gemm_w8.hip): the step's qkv / o_proj / gate_up / down_proj GEMMs read one byte per weight and
+// rebuild bf16(fp8 * row scale) in registers; omni_layer_weights keeps the bf16 copy of the same matrix for the prefill and the fall-backs
+extern "C" int omni_talker_set_dense_w8(omni_talker* t, const omni_dense_w8_layer* layers) {
+    OMNI_CHECK_ARG(t, "omni_talker_set_dense_w8: null engine");
+    if (!layers) { t->w8.clear(); return OMNI_OK; }
+    const omni_talker_desc& d = t->d;
+    OMNI_CHECK_ARG(d.moe_experts == 0, "omni_talker_set_dense_w8: dense backbones only (MoE experts have desc.moe_w8)");
+    OMNI_CHECK_ARG(d.frag_layout && d.fused_norm, "omni_talker_set_dense_w8: needs frag_layout and fused_norm");
+    OMNI_CHECK_ARG(!t->has_ar, "omni_talker_set_dense_w8: single rank only (no peer all-reduce)");
+    for (int l = 0; l < d.layers; ++l) {
+        const omni_dense_w8_layer& w = layers[l];
+        OMNI_CHECK_ARG(w.wqkv && w.wo && w.wgu && w.wdown && w.wqkv_scale && w.wo_scale && w.wgu_scale && w.wdown_scale,
+                       "omni_talker_set_dense_w8: layer %d: null pointer", l);
+    }
+    t->w8.assign(layers, layers + d.layers);
+    return OMNI_OK;
+}
+// ONE predicate for "the backbone runs as persistent launches" -- read by mtp_phase (does the predictor's launch assemble the input and run
+// layer 0's qkv?) and by run_backbone (which then skips that qkv): the two must never disagree (a stale qkv otherwise)
+static bool bb_chain_runs(const omni_talker* t, int B, bool half) {
+    return t->w8.empty() && !(t->has_ar && t->bb_ar_off) && t->d.layers > 0 &&
+           k_bb_chain_supported(t->d, B, t->has_ar ? &t->ar_attn : nullptr, half);
+}
+// the W8 entry points serve the deferred-rstd form only: with omni_debug_gemm_defer(0) the norm-fused GEMMs keep the bf16 kernel
+static bool w8_norm_fused(const omni_talker* t) { return !t->w8.empty() && k_gemm_defer(); }
 // per-layer fp8 KV scales (host arrays [layers]) after a calibration pass: the device copy the captured decode steps read, and the
 // host copy the eager prefill launches pass as arguments
 extern "C" int omni_talker_set_kv_scales(omni_talker* t, const float* k_scale, const float* v_scale, void* stream) {
@@ -733,8 +759,7 @@ static int mtp_phase(omni_talker* t, const omni_step_io* io, void* stream, bool 
     const omni_chain_tail tl{io->input_ids, d.embed, d.vocab, d.cp_embed, io->text_step, io->inputs_embeds, t->resid, t->part, io->audio_codes, d.hidden,
                              d.layers > 0 ? t->layer[0].wqkv : nullptr, d.layers > 0 ? t->layer[0].ln1 : nullptr, t->qkv, (d.q_heads + 2 * d.kv_heads) * d.head_dim};
     // (a tensor-parallel rank too: layer 0's qkv is column-parallel -- this rank's shard, no exchange)
-    const bool want_tail = fuse_tail && d.layers > 0 && !t->chain_half && !(t->has_ar && t->bb_ar_off) &&
-                           k_bb_chain_supported(d, B, t->has_ar ? &t->ar_attn : nullptr, false) && !k_bb_chain_small(d);
+    const bool want_tail = fuse_tail && !t->chain_half && bb_chain_runs(t, B, false) && !k_bb_chain_small(d);
     TRY(run_code_predictor(t, io->input_ids, t->e0, io->last_hidden, B, io->cp_greedy, io->cp_temperature, io->cp_top_k, io->cp_top_p,
                            io->seed, io->steps, nullptr, stream, io->rows.seed, want_tail ? &tl : nullptr));
     if (t->tail_fused) return OMNI_OK;
@@ -752,6 +777,9 @@ static int layer_attn_decode(omni_talker* t, int l, const omni_step_io* io, void
     const omni_layer_weights& w = t->layer[l];
     const int H = d.hidden, hq = d.q_heads, hkv = d.kv_heads, D = d.head_dim, B = io->B;
     if (!with_qkv) {}       // the qkv rows were left by the previous layer's persistent tail (moe_chain.hip moe_tail_kernel)
+    else if (d.fused_norm && w8_norm_fused(t))
+        TRY(omni_gemm_xnorm_w8(t->resid, t->part, l == 0 ? 1 : H / 16, w.ln1, d.eps, t->w8[l].wqkv, t->w8[l].wqkv_scale, t->qkv, B,
+                               (hq + 2 * hkv) * D, H, OMNI_EPI_BF16, 0, st));
     else if (d.fused_norm)  // slab count: 1 after mtp_finalize, H / 16 after any residual GEMM
         TRY(xnorm_gemm(t, t->resid, t->part, l == 0 ? 1 : H / 16, w.ln1, nullptr, w.wqkv, t->qkv, B, (hq + 2 * hkv) * D, H,
                        OMNI_EPI_BF16, nullptr, 0, st));
@@ -772,6 +800,7 @@ static int layer_attn_decode(omni_talker* t, int l, const omni_step_io* io, void
                               OMNI_LAYOUT_W_FRAG | OMNI_LAYOUT_X_FRAG | OMNI_LAYOUT_OUT_FRAG, st));
         return omni_allreduce_resid(&t->ar_attn, t->resid, 1, t->part, 64, nullptr, B, H, st);
     }
+    if (d.fused_norm && !t->w8.empty()) return omni_gemm_resid_w8(t->attn, t->w8[l].wo, t->w8[l].wo_scale, t->resid, 1, t->part, B, H, hq * D, st);
     if (d.fused_norm) return resid_gemm(t->attn, w.wo, t->resid, t->part, B, H, hq * D, st);
     TRY(act_gemm(t, t->attn, w.wo, nullptr, t->attn_out, B, H, hq * D, st));
     return OMNI_OK;
@@ -876,6 +905,15 @@ extern "C" int omni_talker_layer_mlp(omni_talker* t, const omni_step_io* io, int
     }
     if (d.fused_norm) {
         const omni_layer_weights& w = t->layer[layer];
+        if (!t->w8.empty()) {      // (set_dense_w8: single rank, fragment-major -> the GU8 row order)
+            const omni_dense_w8_layer& q8 = t->w8[layer];
+            if (w8_norm_fused(t))
+                TRY(omni_gemm_xnorm_w8(t->resid, t->part, d.hidden / 16, w.ln2, d.eps, q8.wgu, q8.wgu_scale, t->act, io->B, d.inter, d.hidden,
+                                       OMNI_EPI_SILU_MUL_GU8, 1, stream));
+            else
+                TRY(xnorm_gemm(t, t->resid, t->part, d.hidden / 16, w.ln2, nullptr, w.wgu, t->act, io->B, d.inter, d.hidden, silu_epi(t), nullptr, 1, stream));
+            return omni_gemm_resid_w8(t->act, q8.wdown, q8.wdown_scale, t->resid, 1, t->part, io->B, d.hidden, d.inter, stream);
+        }
         TRY(xnorm_gemm(t, t->resid, t->part, d.hidden / 16, w.ln2, nullptr, w.wgu, t->act, io->B, d.inter, d.hidden,
                        silu_epi(t), nullptr, 1, stream));
         if (t->has_ar) {
@@ -953,14 +991,14 @@ static int run_backbone(omni_talker* t, const omni_step_io* io, void* stream, in
     const bool do_attn = (parts & 2) != 0, do_rest = (parts & 4) != 0;
     t->head_fused = false;
 #ifdef OMNI_DEBUG_HOOKS
-    if (parts == 6 && !t->chain_half && k_bb_all_supported(d, io->B, t->has_ar)) {      // A/B arm: the whole stack, attention included, as one persistent launch
+    if (parts == 6 && !t->chain_half && t->w8.empty() && k_bb_all_supported(d, io->B, t->has_ar)) {      // A/B arm: the whole stack, attention included, as one persistent launch
         t->ran |= 2;                                                  // (a split request -- step_part 2 / 4 -- takes the two-launch structure below)
         return k_bb_all(d, t->bb_table, io, t->attn, t->resid, t->part, t->act, t->qkv, t->chain_flags,
                         reinterpret_cast<int32_t*>(t->chain_flags + 320), stream);
     }
 #endif
     const omni_bb_ar bar{&t->ar_attn, &t->ar_mlp};
-    if (!(t->has_ar && t->bb_ar_off) && k_bb_chain_supported(d, io->B, t->has_ar ? &t->ar_attn : nullptr, t->chain_half) && d.layers > 0) {
+    if (bb_chain_runs(t, io->B, t->chain_half)) {
         t->ran |= 2;
         const bool plain = !t->has_ar && !t->chain_half;      // (a tensor-parallel rank / the half grid: the 64-row stage set only)
         // attention launches alternate with one persistent launch per layer: o_proj -> gate_up -> down_proj -> next qkv

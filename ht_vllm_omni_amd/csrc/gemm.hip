@@ -403,6 +403,8 @@ extern "C" void omni_debug_set(int nt, int rn, int wgs) { g_gemm_counted = rn ? 
 extern "C" void omni_debug_tile(int nt, int mt) { g_tile_nt = nt; g_tile_mt = mt; }   // 0 = policy default
 #endif
 
+bool k_gemm_defer() { return g_gemm_defer != 0; }
+
 template <int MT, int NT, int PRO, int EPI>
 static int launch_gemm(const GemmArgs& a_in, int m_splits, hipStream_t st) {
     GemmArgs a = a_in;

@@ -26,6 +26,8 @@ int k_gemm_xnorm(const void* r, const float* partials, int nparts, const void* n
                  const void* w, void* out, int M, int N, int K, int epilogue, const uint8_t* mask, int out_frag, int pstride,
                  void* stream, float mask_fill = -__builtin_inff(),
                  const int32_t* num_live = nullptr /* device: normed_out rows >= *num_live are not written */);
+// do the norm-fused launch-path GEMMs take the deferred-rstd form (PRO 3)?  The product: always; the debug library: omni_debug_gemm_defer
+bool k_gemm_defer();
 // omni_gemm_bf16_ex with the value written for masked-out logits
 int k_gemm_bf16_ex(const void* x, int ldx, const void* w, const void* bias, void* out, int M, int N, int K, int epilogue,
                    const uint8_t* mask, int layout, void* stream, float mask_fill);

@@ -94,6 +94,48 @@ def fp8_dequant_rows(q_u8: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return (q_u8.view(torch.float8_e4m3fn).float() * scale[..., None].float()).to(BF16)
 
 
+def frag_shuffle_w8(q_u8: torch.Tensor) -> torch.Tensor:
+    """[N, K] row-major bytes -> the W8 fragment layout (include/omni_talker.h): per 16-row tile, whole groups of 16 k-steps as
+    eight 1-KB blocks (block w = k-steps w and w + 8 of the group, 16 B per lane), then the k-steps of K % 512 as 512-B blocks of
+    8 B per lane.  A permutation of the bytes; same shape."""
+    N, K = q_u8.shape
+    assert N % 16 == 0 and K % 32 == 0, (N, K)
+    P = K // 512
+    main = q_u8[:, :P * 512].reshape(N // 16, 16, P, 2, 8, 4, 8).permute(0, 2, 4, 5, 1, 3, 6).reshape(N // 16, -1)
+    tail = q_u8[:, P * 512:].reshape(N // 16, 16, K // 32 - 16 * P, 4, 8).permute(0, 2, 3, 1, 4).reshape(N // 16, -1)
+    return torch.cat([main, tail], 1).contiguous().reshape(N, K)
+
+
+def frag_unshuffle_w8(w8: torch.Tensor) -> torch.Tensor:
+    N, K = w8.shape
+    P = K // 512
+    v = w8.reshape(N // 16, 16 * K)
+    main = v[:, :P * 8192].reshape(N // 16, P, 8, 4, 16, 2, 8).permute(0, 4, 1, 5, 2, 3, 6).reshape(N // 16, 16, P * 512)
+    tail = v[:, P * 8192:].reshape(N // 16, K // 32 - 16 * P, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(N // 16, 16, K - P * 512)
+    return torch.cat([main, tail], 2).contiguous().reshape(N, K)
+
+
+def gu8_rows(w: torch.Tensor) -> torch.Tensor:
+    """Rows [gate | up] ([2I, ...]) -> the GU8 row order (gate[8t..8t+7], up[8t..8t+7] per 16-row tile), row-major: what gu8_shuffle
+    applies before the fragment shuffle; used for the fp8 bytes and their row scales alike."""
+    I = w.shape[0] // 2
+    return w.reshape(2, I // 8, 8, *w.shape[1:]).transpose(0, 1).reshape(w.shape)
+
+
+DENSE_NAMES = ("wqkv", "wo", "wgu", "wdown")
+
+
+def dense_fp8_weights(d: TalkerDims, weights: dict) -> dict:
+    """The weights a `dense_fp8` engine computes with: the backbone's four matrices per layer replaced by W_eff = bf16(fp8 * row
+    scale) (fp8_quant_rows / fp8_dequant_rows; a row's scale does not depend on the row order, so quantising before or after the
+    GU8 interleave is the same matrix).  For the oracle and for tests; single rank."""
+    out = dict(weights)
+    for i in range(d.layers):
+        for n in DENSE_NAMES:
+            out[f"l{i}.{n}"] = fp8_dequant_rows(*fp8_quant_rows(weights[f"l{i}.{n}"]))
+    return out
+
+
 def shard_layer(d: TalkerDims, w: dict, prefix: str, rank: int, tp: int) -> dict:
     """Per-rank slices of one backbone layer."""
     D = d.head_dim
@@ -145,7 +187,15 @@ class TalkerEngine:
                  block_size: int = 16, max_batch: int = 64, device: str = "cuda:0", tp_rank: int = 0, tp_size: int = 1,
                  k_scale: float = 1.0, v_scale: float = 1.0, allow_eos: bool = True, masked_logit: float = 0.0, tp_group=None, n_sub: int = 1, tp_force: bool = False, frag_layout: bool = True,
                  fused_norm: bool | None = None, peer_allreduce=None, moe_fp8: bool = False, prefill_gemm: str = "tile",
-                 calculate_kv_scales: bool = False, moe_dispatch: str = "device"):
+                 calculate_kv_scales: bool = False, moe_dispatch: str = "device", dense_fp8: bool = False):
+        # dense backbone decode on fp8 weights (csrc/gemm_w8.hip): the four backbone GEMMs of the decode step stream one byte per weight
+        # and rebuild W_eff = bf16(fp8 * row scale) in registers; the bf16 W_eff copies stay for the prefill and the fall-backs, so
+        # this buys decode bandwidth, not capacity (weight memory of the backbone grows by half)
+        self.dense_fp8 = bool(dense_fp8)
+        if self.dense_fp8 and (dims.moe_experts > 0 or tp_size > 1 or tp_force or peer_allreduce is not None or not frag_layout
+                               or fused_norm is False):
+            raise ValueError("dense_fp8 needs a dense backbone on a single rank with frag_layout and fused_norm "
+                             "(MoE backbones: moe_fp8)")
         if not torch.cuda.is_available():
             raise L.OmniError("TalkerEngine needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
         self.lib = L.load()
@@ -238,10 +288,22 @@ class TalkerEngine:
         if self.fused_norm:
             frag_names += ("moe_router",)      # takes the fused-norm prologue on the norm-free stream (omni_gemm_xnorm: W fragment-major)
         self._layers = (L.LayerWeights * d.layers)()
+        self._w8_layers = (L.DenseW8Layer * d.layers)() if self.dense_fp8 else None
         self._frag_keep: dict = {}
         self.layer_w: list[dict] = []
         for i in range(d.layers):
             sh = shard_layer(d, weights, f"l{i}.", tp_rank, tp_size)
+            if self.dense_fp8:
+                # quantised per output row (after sharding: single rank, so the shard IS the matrix); from here on every consumer --
+                # prefill, fall-backs, the bf16 fragment-major copies in omni_layer_weights -- sees W_eff, and the decode GEMMs get the
+                # bytes in the W8 fragment layout with the scales in the kernel's row order (gate_up: GU8)
+                for n in DENSE_NAMES:
+                    q8, sc = fp8_quant_rows(sh[n])
+                    sh[n] = fp8_dequant_rows(q8, sc)
+                    if n == "wgu":
+                        q8, sc = gu8_rows(q8), gu8_rows(sc)
+                    setattr(self._w8_layers[i], n, up(frag_shuffle_w8(q8.to(dev))).data_ptr())
+                    setattr(self._w8_layers[i], n + "_scale", up(sc.contiguous()).data_ptr())
             if self.moe_fp8:
                 # fp8 e4m3fn expert weights (BASELINE config #5): quantised per output row at load; everything downstream
                 # -- the decode kernels' in-register dequantisation, the prefill's bf16 copies, the oracle in the tests --
@@ -369,6 +431,7 @@ class TalkerEngine:
         self.handle = self.lib.omni_talker_create(C.byref(desc))
         if not self.handle:
             raise L.OmniError("omni_talker_create: " + self.lib.omni_last_error().decode())
+        self._apply_dense_w8(self.handle)
         # ---- sub-batch engines: the decode step is latency-bound (dependent small launches), so independent row ranges
         # of the batch run as concurrent branches of the same hipGraph on separate HIP streams; they share weights and
         # the KV pool and differ only in their scratch (activations, code-predictor KV) and row offset.
@@ -385,6 +448,7 @@ class TalkerEngine:
                 h = self.lib.omni_talker_create(C.byref(dk))
                 if not h:
                     raise L.OmniError("omni_talker_create(sub): " + self.lib.omni_last_error().decode())
+                self._apply_dense_w8(h)
                 self._sub.append((h, sc, dk))
             self._sub_streams = [torch.cuda.Stream(device=dev) for _ in range(self.n_sub)]
             # (round 6: TWO concurrent row ranges CAN keep their backbones' persistent launches on half grids -- set_chains(2), 128 workgroups
@@ -452,6 +516,11 @@ class TalkerEngine:
         else:
             self._ks = self._vs = None
 
+    def _apply_dense_w8(self, handle) -> None:
+        """Hand the fp8 backbone weights to a native engine (after EVERY omni_talker_create: the setting lives in the handle)."""
+        if self.dense_fp8:
+            L.check(self.lib.omni_talker_set_dense_w8(handle, self._w8_layers), "omni_talker_set_dense_w8")
+
     def kv_cache_bytes(self) -> int:
         return sum(c.numel() * c.element_size() for c in self.kv_caches) + sum(s.numel() * 4 for s in (self.kv_scales or []))
 
@@ -474,6 +543,7 @@ class TalkerEngine:
         self.handle = self.lib.omni_talker_create(C.byref(self._desc))
         if not self.handle:
             raise L.OmniError("omni_talker_create: " + self.lib.omni_last_error().decode())
+        self._apply_dense_w8(self.handle)      # per-handle state: a re-created engine starts without it
         self._op_handle = None
         self.calibrate_pending = bool(getattr(self, "_calibrate_requested", False)) and self.kv_code == L.KV_FP8
 

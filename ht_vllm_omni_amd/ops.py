@@ -251,6 +251,43 @@ def gemm_xnorm(r_frag, partials, nparts, norm_w, w_frag, eps, *, M, epilogue=L.E
     return (out, normed) if want_normed else out
 
 
+def gemm_w8(x, w8, w_scale, *, bias=None, layout=0, M=None):
+    """ops.gemm (bf16 epilogue) on fp8 weights: w8 uint8 [N, K] in the W8 fragment layout (engine.frag_shuffle_w8), w_scale
+    fp32 [N]; bit-identical to ops.gemm on frag_shuffle(fp8_dequant_rows(...)).  layout: LAYOUT_X_FRAG / LAYOUT_OUT_FRAG."""
+    _chk_dev(x, w8, w_scale, bias)
+    Mx, K = x.shape
+    M = Mx if M is None else M
+    N = w8.shape[0]
+    rows_out = (M + 15) // 16 * 16 if layout & L.LAYOUT_OUT_FRAG else M
+    out = torch.zeros(rows_out, N, dtype=BF16, device=x.device)
+    L.check(L.load().omni_gemm_w8(L.ptr(x), x.stride(0), L.ptr(w8), L.ptr(w_scale), L.ptr(bias), L.ptr(out), M, N, K, layout,
+                                  L.current_stream()), "omni_gemm_w8")
+    return out
+
+
+def gemm_resid_w8(x_frag, w8, w_scale, r_frag, partials, *, accumulate=True, M=None):
+    """ops.gemm_resid on fp8 weights (x fragment-major): in place on r_frag, fills partials[N/16, 64], returns the slab count."""
+    _chk_dev(x_frag, w8, w_scale, r_frag, partials)
+    Mx, K = x_frag.shape
+    M = Mx if M is None else M
+    N = w8.shape[0]
+    L.check(L.load().omni_gemm_resid_w8(L.ptr(x_frag), L.ptr(w8), L.ptr(w_scale), L.ptr(r_frag), int(accumulate), L.ptr(partials),
+                                        M, N, K, L.current_stream()), "omni_gemm_resid_w8")
+    return N // 16
+
+
+def gemm_xnorm_w8(r_frag, partials, nparts, norm_w, w8, w_scale, eps, *, M, epilogue=L.EPI_BF16, out_frag=False):
+    """ops.gemm_xnorm (deferred-rstd form) on fp8 weights; epilogue EPI_BF16 or EPI_SILU_MUL_GU8 (w8 / w_scale in GU8 row order)."""
+    _chk_dev(r_frag, partials, norm_w, w8, w_scale)
+    K = r_frag.shape[1]
+    N = w8.shape[0] // 2 if epilogue in L.SILU_EPIS else w8.shape[0]
+    rows_out = (M + 15) // 16 * 16 if out_frag else M
+    out = torch.zeros(rows_out, N, dtype=BF16, device=r_frag.device)
+    L.check(L.load().omni_gemm_xnorm_w8(L.ptr(r_frag), L.ptr(partials), nparts, L.ptr(norm_w), float(eps), L.ptr(w8), L.ptr(w_scale),
+                                        L.ptr(out), M, N, K, epilogue, int(out_frag), L.current_stream()), "omni_gemm_xnorm_w8")
+    return out
+
+
 def attn_decode_fused(qkv, qnorm_w, knorm_w, positions, cos_sin, k_cache, v_cache, block_table, seq_lens, *, q_heads,
                       kv_heads, head_dim, block_size, kv_dtype, eps, k_scale=1.0, v_scale=1.0, k_scales=None, v_scales=None,
                       max_seq_len=4096, split=True):

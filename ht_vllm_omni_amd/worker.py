@@ -27,12 +27,23 @@ from .weights import make_weights, weight_bytes
 logger = logging.getLogger("ht_vllm_omni_amd.worker")
 
 
+def _quantization_flags(model: str | TalkerDims, quantization) -> dict:
+    """vLLM's ModelConfig.quantization for the talker stage: "fp8" = weight-only fp8 (e4m3fn bytes + per-row scales computed at load)
+    of the decode step's dominant weight stream -- the dense backbone's GEMMs (engine dense_fp8) or the routed experts of a MoE backbone
+    (engine moe_fp8).  Nothing else is implemented, so nothing else is accepted."""
+    q = str(quantization).lower() if quantization else ""
+    if q not in ("", "none", "fp8"):
+        raise ValueError(f"MI355XARWorker: quantization={quantization!r} is not supported (None or 'fp8')")
+    moe = (model if isinstance(model, TalkerDims) else get_dims(model)).moe_experts > 0
+    return dict(quantization="fp8" if q == "fp8" else None, dense_fp8=q == "fp8" and not moe, moe_fp8=q == "fp8" and moe)
+
+
 def make_config(model: str | TalkerDims = "tts-1.7b", *, kv_cache_dtype: str = "fp8", block_size: int = 16,
                 max_num_seqs: int = 64, tensor_parallel_size: int = 1, gpu_memory_utilization: float = 0.9,
                 num_gpu_blocks_override: int | None = None, weights: dict | None = None, seed: int = 1234,
                 connector: str | None = None, enforce_eager: bool = False, default_sampling_params=None,
                 prompt_builder: dict | None = None, model_path: str | None = None, calculate_kv_scales: bool = False,
-                async_scheduling: bool = False) -> SimpleNamespace:
+                async_scheduling: bool = False, quantization: str | None = None) -> SimpleNamespace:
     if model_path and isinstance(model, str) and model == "tts-1.7b" and os.path.exists(os.path.join(model_path, "config.json")):
         from .checkpoint import dims_from_hf_config
         model = dims_from_hf_config(os.path.join(model_path, "config.json"))          # dimensions come from the checkpoint
@@ -41,7 +52,7 @@ def make_config(model: str | TalkerDims = "tts-1.7b", *, kv_cache_dtype: str = "
                            num_gpu_blocks_override=num_gpu_blocks_override, weights=weights, seed=seed, connector=connector,
                            enforce_eager=enforce_eager, default_sampling_params=default_sampling_params,
                            prompt_builder=prompt_builder, model_path=model_path, calculate_kv_scales=calculate_kv_scales,
-                           async_scheduling=bool(async_scheduling))
+                           async_scheduling=bool(async_scheduling), **_quantization_flags(model, quantization))
 
 
 _PRESET_HINTS = (("omni", "omni-talker"), ("1.7b", "tts-1.7b"), ("0.6b", "tts-0.6b"))
@@ -108,7 +119,8 @@ def config_from_vllm(vllm_config) -> SimpleNamespace:
         enforce_eager=bool(getattr(mc, "enforce_eager", False)), default_sampling_params=extra.get("default_sampling_params"),
         prompt_builder=extra.get("prompt_builder"), model_path=path,
         # scheduler_config.async_scheduling (stage_configs/qwen3_tts.yaml:16): sample_tokens returns an AsyncStepOutput
-        async_scheduling=bool(getattr(sc, "async_scheduling", False)))
+        async_scheduling=bool(getattr(sc, "async_scheduling", False)),
+        **_quantization_flags(model, getattr(mc, "quantization", None)))
 
 
 @dataclass(frozen=True)
@@ -242,7 +254,8 @@ class MI355XARWorker:
         self.engine = TalkerEngine(self.dims, self._weights, kv_dtype=cfg.kv_cache_dtype, num_blocks=int(num_blocks),
                                    block_size=cfg.block_size, max_batch=cfg.max_num_seqs, device=str(self.device),
                                    tp_rank=self.rank, tp_size=self.tp_size, peer_allreduce=self.peer_allreduce,
-                                   calculate_kv_scales=bool(getattr(cfg, "calculate_kv_scales", False)))
+                                   calculate_kv_scales=bool(getattr(cfg, "calculate_kv_scales", False)),
+                                   dense_fp8=bool(getattr(cfg, "dense_fp8", False)), moe_fp8=bool(getattr(cfg, "moe_fp8", False)))
         # ... and the all-reduce INSIDE the backbone's persistent launches only after four scratch steps both ways agreed on every rank
         self.tp_backbone_chain = False
         if self.peer_allreduce is not None:

@@ -245,6 +245,32 @@ int omni_gemm_xnorm(const void* r, const float* partials, int nparts, const void
                     const void* w, void* out, int M, int N, int K, int epilogue, const uint8_t* mask, int out_frag,
                     void* stream);
 
+/* The same skinny GEMMs on fp8 e4m3fn WEIGHTS (csrc/gemm_w8.hip): w8 holds one byte per weight, w_scale fp32 [rows] one
+ * scale per output row, and the kernel multiplies by W_eff = bf16(fp8 * scale) rebuilt in registers -- the decode step streams
+ * half the bytes.  Every entry point returns bit for bit what its bf16 counterpart returns on a fragment-major W_eff
+ * (omni_gemm_bf16_ex / omni_gemm_resid / omni_gemm_xnorm in its default deferred-rstd form).  M <= 64, N % 16 == 0,
+ * K % 32 == 0, scales required; anything else is OMNI_EINVAL.
+ *
+ * W8 fragment layout of a [N, K] byte matrix (the counterpart of OMNI_LAYOUT_W_FRAG; engine.frag_shuffle_w8): 16-row tiles
+ * of 16 * K bytes, tile t = rows 16 t .. 16 t + 15.  Inside a tile, with k-steps s = k / 32 and P = K / 512 whole groups of
+ * 16 k-steps:
+ *   s <  16 P:  byte (row, k) at  ((s / 16) * 8 + s % 8) * 1024 + ((k % 32) / 8 * 16 + row % 16) * 16 + ((s % 16) / 8) * 8 + k % 8
+ *               -- a 1-KB block holds k-steps s and s + 8 of one 16-step group (consecutive steps of one wave of the kernel),
+ *               16 B per lane: 8 bytes of step s, then 8 bytes of step s + 8;
+ *   s >= 16 P:  byte (row, k) at  P * 8192 + (s - 16 P) * 512 + ((k % 32) / 8 * 16 + row % 16) * 8 + k % 8
+ *               -- the remaining k-steps (K % 512 != 0) as 512-B blocks of 8 B per lane.
+ * The layout is a permutation of the N * K bytes.
+ *   omni_gemm_w8:       out bf16 = bf16(x . W_eff^T + bias); layout: OMNI_LAYOUT_X_FRAG / OMNI_LAYOUT_OUT_FRAG (W is always W8)
+ *   omni_gemm_resid_w8: omni_gemm_resid on a fragment-major x, no bias; partials[N/16][64]
+ *   omni_gemm_xnorm_w8: omni_gemm_xnorm with epilogue OMNI_EPI_BF16 or OMNI_EPI_SILU_MUL_GU8 (w8 / w_scale then in the GU8
+ *                       row order, 2 * N rows), no mask, no normed_out                                                      */
+int omni_gemm_w8(const void* x, int ldx, const void* w8, const float* w_scale, const void* bias, void* out, int M, int N, int K,
+                 int layout, void* stream);
+int omni_gemm_resid_w8(const void* x_frag, const void* w8, const float* w_scale, void* r_io, int accumulate, float* partials,
+                       int M, int N, int K, void* stream);
+int omni_gemm_xnorm_w8(const void* r, const float* partials, int nparts, const void* norm_w, float eps, const void* w8,
+                       const float* w_scale, void* out, int M, int N, int K, int epilogue, int out_frag, void* stream);
+
 /* Per-head q/k RMSNorm + neox RoPE + KV-cache write with quantisation
  * (vLLM Qwen3Attention q_norm/k_norm + rotary_emb + reshape_and_cache; slot mapping built at
  * V/worker/gpu_ar_model_runner.py:239-244, passed via set_forward_context 283-292).
@@ -489,6 +515,19 @@ int omni_talker_set_chains(omni_talker* t, int on);
 /* Which persistent chains the LAST decode-step call of this engine launched (host-side record, no device access):
  * bit 0 the code-predictor chain (cp_chain.hip), bit 1 the backbone chain (bb_chain.hip).  0 = launch-per-op path.      */
 int omni_talker_chains_ran(const omni_talker* t);
+/* Dense backbone decode on fp8 weights (additive to ABI v5).  layers = HOST array [desc.layers] of device pointers: the four
+ * backbone matrices of every layer as fp8 bytes in the W8 fragment layout (wgu in the GU8 row order first) and their fp32 row
+ * scales, quantised so that bf16(fp8 * scale) IS the bf16 matrix in omni_layer_weights (which the prefill and every fall-back
+ * keep reading); the array is copied.  From then on the decode step runs the backbone launch per op on omni_gemm_xnorm_w8 /
+ * omni_gemm_resid_w8 -- same bits as before, half the weight bytes; the backbone's persistent launches are not used
+ * (omni_talker_chains_ran bit 1 stays clear), the code predictor, the lm_head and the prefill are unchanged.  NULL switches it
+ * off.  Needs a dense backbone (moe_experts == 0), frag_layout, fused_norm and no peer all-reduce: OMNI_EINVAL otherwise.
+ * Call before capturing graphs.                                                                                          */
+typedef struct omni_dense_w8_layer {
+    const void *wqkv, *wo, *wgu, *wdown;
+    const float *wqkv_scale, *wo_scale, *wgu_scale, *wdown_scale;
+} omni_dense_w8_layer;
+int omni_talker_set_dense_w8(omni_talker* t, const omni_dense_w8_layer* layers);
 /* ABI v4.  Per-layer fp8 KV scales (host arrays [layers], all > 0) -- the result of a `calculate_kv_scales` pass: the reference
  * runs its first forward eager so that vLLM's attention layers can set k_scale = max|k| / 200, v_scale = max|v| / 100 from that
  * pass (V/worker/gpu_ar_model_runner.py:122,269-275).  The decode step's attention launches read the scales

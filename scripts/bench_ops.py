@@ -83,8 +83,71 @@ def bench_attn(name, B, hq, hkv, ctx, kv, layers, fused):
     kvb = B * ctx * hkv * D * 2 * (1 if kv == "fp8" else 2)
     print(f"{name:26s} B={B} ctx={ctx} {kv} fused={fused}: {us:6.2f} us  {kvb/1e6:6.1f} MB {kvb/us/1e6:5.2f} TB/s", flush=True)
 
+def bench_w8(rounds=9, reps=3, M=64):
+    """The four 1.7B backbone GEMMs at M = 64 as the decode step launches them (qkv: deferred-rstd prologue; o / down: residual epilogue;
+    gate_up: deferred-rstd + GU8): the W8 entry point against the bf16 entry point on W_eff.  Cold weights (rotating sets past the 256 MB
+    of MALL in BOTH arms), caller-allocated outputs (no fill kernel in the graph), arms alternated round by round in this one process;
+    prints median and min-max of every arm -- the bf16 arm's spread is the yardstick of the ratio."""
+    from ht_vllm_omni_amd.engine import frag_shuffle, frag_shuffle_w8, gu8_shuffle, gu8_rows, fp8_quant_rows, fp8_dequant_rows
+    st = L.current_stream
+    for name, form, N, K in (("qkv", "xnorm", 4096, 2048), ("o_proj", "resid", 2048, 2048), ("gate_up", "gu8", 6144, 2048), ("down", "resid", 2048, 6144)):
+        rows = 2 * N if form == "gu8" else N
+        R = max(4, min(64, int(1.2e9 // (rows * K * 2))))
+        sets = []
+        for _ in range(R):
+            q8, sc = fp8_quant_rows((torch.randn(rows, K, device=dev) * 0.02).to(BF16))
+            weff = fp8_dequant_rows(q8, sc)
+            if form == "gu8":
+                sets.append((frag_shuffle_w8(gu8_rows(q8)), gu8_rows(sc).contiguous(), gu8_shuffle(weff)))
+            else:
+                sets.append((frag_shuffle_w8(q8), sc, frag_shuffle(weff)))
+        x = frag_shuffle(torch.randn(M, K, device=dev, dtype=BF16))
+        nw = torch.ones(K, device=dev, dtype=BF16)
+        part = torch.rand(K // 16, 64, device=dev) + 0.5
+        out = torch.zeros(M, N, device=dev, dtype=BF16)
+        slabs = torch.zeros(N // 16, 64, device=dev)
+        epi = L.EPI_SILU_MUL_GU8 if form == "gu8" else L.EPI_BF16
+        def run(arm):
+            for w8, sc, wf in sets:
+                if form == "resid" and arm:
+                    rc = lib.omni_gemm_resid_w8(x.data_ptr(), w8.data_ptr(), sc.data_ptr(), out.data_ptr(), 1, slabs.data_ptr(), M, N, K, st())
+                elif form == "resid":
+                    rc = lib.omni_gemm_resid(x.data_ptr(), K, wf.data_ptr(), None, out.data_ptr(), 1, slabs.data_ptr(), None, M, N, K,
+                                             L.LAYOUT_W_FRAG | L.LAYOUT_X_FRAG, st())
+                elif arm:
+                    rc = lib.omni_gemm_xnorm_w8(x.data_ptr(), part.data_ptr(), K // 16, nw.data_ptr(), 1e-6, w8.data_ptr(), sc.data_ptr(), out.data_ptr(),
+                                                M, N, K, epi, int(form == "gu8"), st())
+                else:
+                    rc = lib.omni_gemm_xnorm(x.data_ptr(), part.data_ptr(), K // 16, nw.data_ptr(), 1e-6, None, wf.data_ptr(), out.data_ptr(), M, N, K, epi,
+                                             None, int(form == "gu8"), st())
+                L.check(rc, name)
+        graphs = []
+        for arm in (0, 1):
+            run(arm); torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                run(arm)
+            g.replay(); torch.cuda.synchronize()
+            graphs.append(g)
+        t = ([], [])
+        for _ in range(rounds):
+            for arm in (0, 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps): graphs[arm].replay()
+                e1.record(); torch.cuda.synchronize()
+                t[arm].append(e0.elapsed_time(e1) / (reps * R) * 1e3)
+        med = [sorted(v)[len(v) // 2] for v in t]
+        byts = [rows * K * 2, rows * K + rows * 4]
+        print(f"{name:8s} {rows:5d} x {K:4d} M={M} sets={R} | " + " | ".join(
+            f"{a}: {med[i]:6.2f} us (min {min(t[i]):6.2f} max {max(t[i]):6.2f}) {byts[i] / med[i] / 1e6:5.2f} TB/s" for i, a in enumerate(("bf16", "w8  "))) +
+            f" | w8 / bf16 = {med[1] / med[0]:.3f}  (bf16 spread +-{(max(t[0]) - min(t[0])) / 2 / med[0]:.1%})", flush=True)
+        del sets
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["gemm", "norm", "attn"]
+    if "w8" in which:
+        bench_w8()
     if "gemm" in which:
         bench_gemm("bb qkv", 4096, 2048, L.EPI_BF16)
         bench_gemm("bb o_proj", 2048, 2048, L.EPI_BF16)
