@@ -7,7 +7,7 @@
 #include "common.cuh"
 #include "gemm_frag.cuh"
 
-#define CH_WAVES 8
+#define CH_WAVES SKINNY_WAVES
 #define CH_THREADS (CH_WAVES * 64)
 
 // ---- in-kernel timeline of a stage (libomni_talker_debug.so only; scripts/chain_timeline.py): wave 0 of every workgroup
@@ -157,12 +157,7 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
     if (NORM) {
         const coh_rsrc_t prs = coh_rsrc(part_in);
         const int row = lane % XROWS, sub = lane / XROWS;
-#pragma unroll
-        for (int e = 0; e < SO::PE; ++e) {
-            const int p = SO::index(wave, sub, e);
-            pv[e] = coh_ldf(prs, (uint32_t)(min(p, np_in - 1) * PS + m_base + row) * 4);
-            if (p >= np_in) pv[e] = 0.f;
-        }
+        SO::gather(pv, wave, sub, np_in, [&](int p) { return coh_ldf(prs, (uint32_t)(p * PS + m_base + row) * 4); });
     }
     u32x4 Xq[G][MT];
     auto load_x = [&](int d) {           // k-step d of this wave's share into ring slot d % G
@@ -193,10 +188,7 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
         // fixed-order reduction of the slabs -> rstd of this workgroup's rows (gemm.hip xnorm_rstd, same order of additions)
         red[wave * 64 + lane] = SO::reduce(pv);
         chain_barrier(g);
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < CH_WAVES; ++w) t += red[w * 64 + lane];
-        const float rl = 1.0f / sqrtf(t / (float)K + eps);
+        const float rl = row_rstd(red, lane, K, eps);
 #pragma unroll
         for (int i = 0; i < MT; ++i) rstd[i] = __shfl(rl, i * 16 + (lane & 15), 64);
     }
@@ -273,10 +265,7 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
         const int m = m_base + ml, n = bx * 16 + 4 * (l >> 4);
         const uint32_t off = (uint32_t)frag_off(has ? m : m_base, n, N) * 2;
         f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (has) {
-#pragma unroll
-            for (int w = 0; w < CH_WAVES; ++w) sum += lds4[(w * TP + tl) * 64 + l];
-        }
+        if (has) sum = combine_waves(lds4, TP, tl, l);
         const u32x2 mine = (u32x2){pack_bf2(sum[0], sum[1]), pack_bf2(sum[2], sum[3])};      // this rank's partial, bf16
         float acc[4] = {bf_lo(mine[0]), bf_hi(mine[0]), bf_lo(mine[1]), bf_hi(mine[1])};
         const int world = ar->world, rank = ar->rank;
@@ -321,17 +310,11 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
                 }
             }
         }
-        float rv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (has) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rv[e] = bfround(acc[e]);               // the all-reduced delta, bf16 (one rank: the partial itself)
-            rv[0] = bfround(bf_lo(r_old[0]) + rv[0]); rv[1] = bfround(bf_hi(r_old[0]) + rv[1]);
-            rv[2] = bfround(bf_lo(r_old[1]) + rv[2]); rv[3] = bfround(bf_hi(r_old[1]) + rv[3]);
-            coh_st8(ors, off, (u32x2){pack_bf2(rv[0], rv[1]), pack_bf2(rv[2], rv[3])});
-        }
-        float ss = sq4_sum(rv[0], rv[1], rv[2], rv[3]);
-        ss = xor32_sum(xor16_sum(ss));                                         // (whole waves: rows past Mloc add into lanes nobody stores)
-        if (has && l < 16) coh_st4(coh_rsrc(part_out), (uint32_t)(bx * PS + m) * 4, __float_as_uint(ss));
+        // the all-reduced delta, rounded to bf16 (one rank: the partial itself), into the residual epilogue.  Whole waves: a thread without
+        // an item enters with zeros (acc and r_old), and its row past Mloc adds into lanes nobody stores
+        const ResidOut ro = resid_values(acc, r_old, true);
+        if (has) coh_st8(ors, off, ro.r);
+        if (has && l < 16) coh_st4(coh_rsrc(part_out), (uint32_t)(bx * PS + m) * 4, __float_as_uint(ro.ss));
     } else
     for (int it = threadIdx.x; it < ITEMS; it += CH_THREADS) {
         const int l = it % LN;
@@ -340,19 +323,11 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
         const int ml = i * 16 + (l & 15);
         if (ml >= Mloc) continue;
         const int m = m_base + ml;
-        f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f}, sum2 = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < CH_WAVES; ++w) {
-            sum += lds4[(w * TP + tl) * 64 + l];
-            if (GU8) sum2 += lds4[(w * TP + tl) * 64 + l + 32];
-            if (SILU2) sum2 += lds4[(w * TP + (NT / 2 + j) * MT + i) * 64 + l];
-        }
+        f32x4 sum = combine_waves(lds4, TP, tl, l), sum2 = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (GU8) sum2 = combine_waves(lds4, TP, tl, l + 32);
+        if (SILU2) sum2 = combine_waves(lds4, TP, (NT / 2 + j) * MT + i, l);
         if (DEFER) {
-            // rstd of this item's row: the eight wave partials of the slab reduction, in wave order (the combine barrier covered them)
-            float tsum = 0.f;
-#pragma unroll
-            for (int w = 0; w < CH_WAVES; ++w) tsum += red[w * 64 + ml];
-            const float rl = 1.0f / sqrtf(tsum / (float)K + eps);
+            const float rl = row_rstd(red, ml, K, eps);      // this item's row (the combine barrier covered the wave partials)
             sum *= rl;
             if (GU8 || SILU2) sum2 *= rl;
         }
@@ -373,15 +348,10 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
             coh_st8(ors, (uint32_t)frag_off(m, n, N) * 2, (u32x2){pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])});
         } else if (EPI == OMNI_EPI_RESID) {
             const int n = bx * 16 + 4 * (l >> 4);
-            float rv[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rv[e] = bfround(sum[e]);
-            rv[0] = bfround(bf_lo(r_old[0]) + rv[0]); rv[1] = bfround(bf_hi(r_old[0]) + rv[1]);
-            rv[2] = bfround(bf_lo(r_old[1]) + rv[2]); rv[3] = bfround(bf_hi(r_old[1]) + rv[3]);
-            coh_st8(ors, (uint32_t)frag_off(m, n, N) * 2, (u32x2){pack_bf2(rv[0], rv[1]), pack_bf2(rv[2], rv[3])});
-            float ss = sq4_sum(rv[0], rv[1], rv[2], rv[3]);
-            ss = xor32_sum(xor16_sum(ss));
-            if (l < 16) coh_st4(coh_rsrc(part_out), (uint32_t)(bx * PS + m) * 4, __float_as_uint(ss));
+            const float v[4] = {sum[0], sum[1], sum[2], sum[3]};
+            const ResidOut ro = resid_values(v, r_old, true);
+            coh_st8(ors, (uint32_t)frag_off(m, n, N) * 2, ro.r);
+            if (l < 16) coh_st4(coh_rsrc(part_out), (uint32_t)(bx * PS + m) * 4, __float_as_uint(ro.ss));
         } else if (EPI == OMNI_EPI_F32_BF16RND) {
             // logits: fp32 cells holding bf16-rounded values (the reference's bf16 head output), row-major
             const int n = (bx * NT + j) * 16 + 4 * (l >> 4);

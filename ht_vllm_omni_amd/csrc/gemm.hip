@@ -26,22 +26,18 @@
 #include "common.cuh"
 #include "kernels.h"
 #include "gemm_frag.cuh"
+#include "skinny_epi.cuh"
+#include "gemm_tile_policy.h"
 
-#define GEMM_WAVES 8
-#define GEMM_THREADS (GEMM_WAVES * 64)
+#define GEMM_WAVES SKINNY_WAVES
+#define GEMM_THREADS SKINNY_THREADS
 
-struct GemmArgs {
+struct GemmArgs : SkinnyArgs {
     const uint16_t* x; int ldx;
-    const uint16_t* W; const uint16_t* bias; void* out;
-    int M, N, K;
-    const uint8_t* mask;
-    // EPI_RESID: resid = the stream to add into (NULL: start a new one); PRO_XNORM: norm_w / eps / normed_out (row-major copy)
-    const uint16_t* resid; const uint16_t* norm_w; float eps; uint16_t* normed_out;
-    int wshuf, xshuf, oshuf;   // fragment-major layouts (OMNI_LAYOUT_*), see common.cuh frag_off
-    // PRO_XNORM / EPI_RESID: per-row sum-of-squares slabs [np][64 rows] fp32 (deterministic: one slab per producer workgroup)
-    const float* part_in; int np_in; float* part_out;
-    int pstride;               // rows per slab (64; 128 for the code predictor's two-position pass)
-    float mask_fill;           // logit written where mask[n] == 0 (-inf; the Omni talker writes -1e9)
+    const uint16_t* W;
+    // PRO_XNORM: norm_w (eps: SkinnyArgs) / normed_out (row-major copy)
+    const uint16_t* norm_w; uint16_t* normed_out;
+    int wshuf, xshuf;          // fragment-major layouts (OMNI_LAYOUT_*), see common.cuh frag_off
     int counted;               // use the counted (unpredicated, 2-deep) schedule when K % 512 == 0
     const int32_t* num_live;   // PRO_XNORM normed_out: rows >= *num_live are not written (NULL: all M rows)
     int dbg_stage;             // debug library only: leave the kernel after stage N (launch-cost attribution), 0 = run all
@@ -52,8 +48,10 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_skinny_kernel(const GemmArg
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [WAVES][NT*MT*4][64]
 #ifdef OMNI_DEBUG_HOOKS
 #define DBG_STAGE(n) if (a.dbg_stage == (n)) return
+#define DBG_STAGE_NOW a.dbg_stage
 #else
 #define DBG_STAGE(n)
+#define DBG_STAGE_NOW 0
 #endif
     DBG_STAGE(1);                                                  // 1: empty kernel with this launch geometry
     const int lane = threadIdx.x & 63;
@@ -99,59 +97,26 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_skinny_kernel(const GemmArg
 #pragma unroll
         for (int i = 0; i < MT; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // PRO_XNORM, part 1: this thread's share of the sum(r^2) slabs of the workgroup's OWN rows (row = t % rows, every
-    // NCH-th slab; slabs are [n group][64 rows], so a wave-level load is contiguous) -- issued BEFORE the W ring so that
-    // it returns first (loads complete in order) and the reduction overlaps the W latency.  Loads are unconditional
-    // (clamped slab index): a predicated load would force hipcc to drain every outstanding load at each wait.
+    // PRO_XNORM, part 1, and the old residual values of EPI_RESID (skinny_epi.cuh) -- issued BEFORE the W ring so that they return first
+    // (loads complete in order) and the slab reduction overlaps the W latency.
     // PRO 3 (round 6; the chains' DEFER form, chain_gemm.cuh): the row's rstd is NOT folded into the operand fragments -- x = bf16(w * r)
     // -- but multiplies the fp32 sums in the epilogue: the slab reduction leaves the critical path between the operand loads and the first
     // MFMA (one LDS round trip + a workgroup barrier per norm-fused GEMM).  One rounding point moves: rstd * sum(W * bf16(w r)) instead of
     // sum(W * bf16(w * bf16(r rstd))) -- one bf16 rounding per element instead of two; gated on the accuracy tests (tests/test_gpu_parity_full.py
     // three-way statement), not on the oracle's bits.  Taken for the GEMMs whose normalised rows are nobody's output (qkv, gate_up).
     constexpr bool NORM = PRO == 2 || PRO == 3, DEFER = PRO == 3;
-    constexpr int XROWS = MT * 16, NCH = GEMM_THREADS / XROWS;
-    typedef SlabOrder<XROWS> SO;                                                  // canonical slab order (gemm_frag.cuh): SO::PE slabs per thread cover np <= 128
-    float pv[SO::PE];
-    float psum = 0.f;
-    if (NORM) {
-        const int row = lane % XROWS, sub = lane / XROWS, ch = threadIdx.x / XROWS;
-        const float* pp = a.part_in + m_base + row;
-#pragma unroll
-        for (int e = 0; e < SO::PE; ++e) {
-            const int p = SO::index(wave, sub, e);
-            pv[e] = pp[(size_t)min(p, a.np_in - 1) * a.pstride];
-            if (p >= a.np_in) pv[e] = 0.f;
-        }
-        for (int p = ch + 128; p < a.np_in; p += NCH) psum += pp[(size_t)p * a.pstride];      // hidden > 2048 only (no chain there)
-    }
-    // EPI_RESID: the old residual values this thread will add into (one epilogue item per thread), fetched up front
-    uint2 r_old = make_uint2(0, 0);
-    if (EPI == OMNI_EPI_RESID && a.resid && threadIdx.x < MT * 64) {
-        const int ml = (threadIdx.x >> 6) * 16 + (lane & 15);
-        if (ml < Mloc)
-            r_old = *reinterpret_cast<const uint2*>(a.resid + frag_off(m_base + ml, blockIdx.x * 16 + 4 * (lane >> 4), N));
-    }
+    SkinnyPro<MT, NORM, EPI> pro;
+    pro.load(a, m_base, Mloc);
 
     DBG_STAGE(2);                                                  // 2: + addressing, slab / old-residual loads issued
     float rstd[MT];
     auto xnorm_rstd = [&]() {
-        // part 2 (after the W ring is in flight): fixed-order reduction -> rstd of this workgroup's rows.  row = lane % XROWS:
-        // fold the channels that share a wave by shuffles, the 8 waves through a private LDS area past the epilogue's
+        // PRO 2, part 2 (after the W ring is in flight): rstd of this workgroup's rows through a private LDS area past the epilogue's
         // (ONE barrier; every wave then holds all row sums and picks its MFMA rows by shuffle)
-        float s_ = SO::reduce(pv);
-        if (a.np_in > 128) {                                   // the slabs past the canonical 128: folded over the row's channels as before
-            if (XROWS <= 32) psum = xor32_sum(psum);
-            if (XROWS <= 16) psum = xor16_sum(psum);
-            s_ += psum;
-        }
-        float* red = lds + GEMM_WAVES * NT * MT * 4 * 64;      // past the combine slots
-        red[wave * 64 + lane] = s_;
-        if (DEFER) return;                                     // read behind the combine barrier, by the epilogue
+        float* red = skinny_red<MT, NT>(lds);
+        pro.reduce_to(a, red);
         __syncthreads();
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < GEMM_WAVES; ++w) t += red[w * 64 + lane];
-        const float rl = 1.0f / sqrtf(t / (float)K + a.eps);
+        const float rl = row_rstd(red, lane, K, a.eps);
 #pragma unroll
         for (int i = 0; i < MT; ++i) rstd[i] = __shfl(rl, i * 16 + r, 64);
     };
@@ -276,8 +241,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_skinny_kernel(const GemmArg
         }
     }
 
-    if (DEFER) xnorm_rstd();      // PRO 3: the slab reduction behind the MFMA loop (its loads returned ahead of the operands'); read by the epilogue
-    DBG_STAGE(3);                                                  // 3: + main loop (operand loads, normalisation, MFMA)
+    // 3: + main loop (operand loads, normalisation, MFMA) -- here for PRO 2, whose extra pass follows; for the other forms inside
+    // skinny_finish, behind PRO 3's slab reduction
+    if (PRO == 2) { DBG_STAGE(3); }
     // the normalised rows themselves (h[t+1] of the final norm) leave row-major, spread over the n groups: workgroup column x
     // re-reads the (L2-hot) fragments of k-steps x, x + gridDim.x, ... of its rows -- a second pass kept out of the main loop so
     // that its waits stay counted, and short (one k-step per wave at most) so that no workgroup column carries a tail
@@ -294,106 +260,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_skinny_kernel(const GemmArg
         }
     }
 
-    // ---- combine the 8 K-partials through LDS: one 16-byte slot per (wave, tile, lane) holding the lane's 4 accumulator
-    // registers -- ds_write_b128 / ds_read_b128, a quarter of the LDS instructions of the former [wave][reg][lane] floats
-    // (GEMM stage attribution, scripts/ab_knobs.py gemm_stage: the combine + epilogue were 0.42 ms of a 3.93 ms step)
-    f32x4* lds4 = reinterpret_cast<f32x4*>(lds);
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) lds4[(wave * (NT * MT) + j * MT + i) * 64 + lane] = acc[j][i];
-    __syncthreads();
-    DBG_STAGE(4);                                                  // 4: + LDS write of the K partials + barrier
-
-    // item = (m-tile i, [n-tile j], lane l): 4 consecutive n (reg 0..3) of one row m
-    // OMNI_EPI_SILU_MUL_GU8: every 16-row W tile = 8 gate rows (D lanes 0..31) + the 8 matching up rows (lanes 32..63)
-    constexpr bool GU8 = EPI == OMNI_EPI_SILU_MUL_GU8;
-    constexpr bool SILU = EPI == OMNI_EPI_SILU_MUL || GU8;
-    constexpr int NTO = (EPI == OMNI_EPI_SILU_MUL) ? NT / 2 : NT;
-    constexpr int LN = GU8 ? 32 : 64;
-    constexpr int ITEMS = NTO * MT * LN;
-    for (int it = threadIdx.x; it < ITEMS; it += GEMM_THREADS) {
-        const int l = it % LN;
-        const int t = it / LN;
-        const int i = t % MT, j = t / MT;
-        const int ml = i * 16 + (l & 15);
-        if (ml >= Mloc) continue;
-        const int m = m_base + ml;
-        float v[4], v2[4];
-        {
-            f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f}, sum2 = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int w = 0; w < GEMM_WAVES; ++w) {              // fixed order: run-to-run deterministic
-                sum += lds4[(w * (NT * MT) + j * MT + i) * 64 + l];
-                if (EPI == OMNI_EPI_SILU_MUL) sum2 += lds4[(w * (NT * MT) + (NT / 2 + j) * MT + i) * 64 + l];
-                if (GU8) sum2 += lds4[(w * (NT * MT) + j * MT + i) * 64 + l + 32];
-            }
-            if (DEFER) {
-                // rstd of this item's row: the eight wave partials of the slab reduction, in wave order (the combine barrier covered them)
-                const float* red = lds + GEMM_WAVES * NT * MT * 4 * 64;
-                float tsum = 0.f;
-#pragma unroll
-                for (int w = 0; w < GEMM_WAVES; ++w) tsum += red[w * 64 + ml];
-                const float rl = 1.0f / sqrtf(tsum / (float)K + a.eps);
-                sum *= rl;
-                if (SILU) sum2 *= rl;
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) { v[g] = sum[g]; v2[g] = sum2[g]; }
-        }
-        if (SILU) {
-            const int n = GU8 ? (blockIdx.x * NT + j) * 8 + 4 * (l >> 4) : blockIdx.x * 16 * (NT / 2) + j * 16 + 4 * (l >> 4);
-            float o[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                // HF: down(silu(gate(x)) * up(x)) with bf16 tensors: each op rounds to bf16
-                const float gt = bfround(v[g]);
-                const float up = bfround(v2[g]);
-                const float sl = bfround(gt / (1.0f + expf(-gt)));
-                o[g] = sl * up;
-            }
-            *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + (a.oshuf ? frag_off(m, n, N) : (size_t)m * N + n)) =
-                make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
-        } else {
-            const int n = blockIdx.x * 16 * NT + j * 16 + 4 * (l >> 4);
-            if (a.bias) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) v[g] += bf2f(a.bias[n + g]);
-            }
-            if (EPI == OMNI_EPI_RESID) {
-                // r = bf16(r + bf16(acc)) in place on the fragment-major residual stream (every element has exactly one
-                // owner thread), plus this workgroup's 16-column share of sum(r^2) per row for the consumer's RMSNorm
-                static_assert(EPI != OMNI_EPI_RESID || NT == 1, "EPI_RESID: one n-tile per workgroup");
-                uint16_t* rp = reinterpret_cast<uint16_t*>(a.out) + frag_off(m, n, N);
-                float rv[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) rv[g] = bfround(v[g]);
-                if (a.resid) {     // item == thread (ITEMS = MT * 64 <= 256): r_old was fetched for exactly this (m, n)
-                    rv[0] = bfround(bf_lo(r_old.x) + rv[0]); rv[1] = bfround(bf_hi(r_old.x) + rv[1]);
-                    rv[2] = bfround(bf_lo(r_old.y) + rv[2]); rv[3] = bfround(bf_hi(r_old.y) + rv[3]);
-                }
-                *reinterpret_cast<uint2*>(rp) = make_uint2(pack_bf2(rv[0], rv[1]), pack_bf2(rv[2], rv[3]));
-                float ss = sq4_sum(rv[0], rv[1], rv[2], rv[3]);
-                ss = xor32_sum(xor16_sum(ss));       // the 4 lanes (l & 15) + 16 * {0..3} hold the 16 columns of row m
-                if (l < 16) a.part_out[blockIdx.x * a.pstride + m] = ss;   // slabs [n group][pstride rows]
-            } else if (EPI == OMNI_EPI_BF16) {
-                *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + (a.oshuf ? frag_off(m, n, N) : (size_t)m * N + n)) =
-                    make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
-            } else {
-                float4 o;
-                float* po = reinterpret_cast<float*>(&o);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float y = (EPI == OMNI_EPI_F32_BF16RND) ? bfround(v[g]) : v[g];
-                    if (a.mask && !a.mask[n + g]) y = a.mask_fill;
-                    po[g] = y;
-                }
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + (size_t)m * N + n) = o;
-            }
-        }
-    }
+    // ---- [PRO 3: the slab reduction,] the LDS combine of the 8 K-partials and the epilogue
+    skinny_finish<MT, NT, PRO, EPI>(a, lds, acc, pro, m_base, Mloc, DBG_STAGE_NOW);
 }
-
 
 OMNI_KNOB g_gemm_nt = 1, g_gemm_wgs = 256, g_tile_nt = 0, g_tile_mt = 0, g_gemm_counted = 1, g_gemm_stage = 0, g_gemm_defer = 1;
 #ifdef OMNI_DEBUG_HOOKS
@@ -425,50 +294,24 @@ static int launch_gemm(const GemmArgs& a_in, int m_splits, hipStream_t st) {
     return OMNI_OK;
 }
 
-// Tile policy.  Plain GEMMs: narrow n groups (NT = 1, SiLU 16 + 16 columns), M split over grid.y until the grid has
-// ~256 workgroups.  PRO_XNORM: wide n groups (NT = 4) and as many M splits as that allows -- the normalisation work
-// of a workgroup is proportional to the rows it owns, and is repeated once per n group.
-static void pick_tile(int pro, int epi, const GemmArgs& a, int* nt_out, int* mt_out, int* splits_out) {
-    const int mt_total = (a.M + 15) / 16;
-    const bool gu8 = epi == OMNI_EPI_SILU_MUL_GU8;
-    const bool silu = epi == OMNI_EPI_SILU_MUL || gu8;
+// The tile policy (gemm_tile_policy.h) with the debug library's knobs between and behind its two steps
+static void pick_tile(bool norm, int epi, const GemmArgs& a, int* nt_out, int* mt_out, int* splits_out) {
+    int nt = skinny_tile_nt(norm, epi, a.M, a.N, a.K);
+    const bool gu8 = epi == OMNI_EPI_SILU_MUL_GU8, silu = epi == OMNI_EPI_SILU_MUL || gu8;
     const int cols = silu ? a.N / 8 : a.N / 16;               // n groups at the narrowest tile
-    int nt = silu ? 2 : 1;
-    if (pro == 2) {
-        // measured at M = 64 (scripts/bench_tiles.py): 64+ groups of NT = 4, else NT = 2
-        nt = (cols % 4 == 0 && cols / 4 >= 64) ? 4 : ((cols % 2 == 0 && cols / 2 >= 32) ? 2 : nt);
-        // 4096 columns over K >= 2048 (the backbone's qkv): 128 groups x 2 m-splits beat 64 x 4 (10.4 vs 10.8 us; the code
-        // predictor's K = 1024 shape does not: same-box A/B of the step)
-        // (33-48 rows -- three 16-row tiles -- take the 64-row choice too since round 5: 128 groups x 2 m-splits of 32 rows, the tile set of
-        //  the persistent backbone launch, which now runs from 33 rows on: bb_chain.hip)
-        if (!silu && nt == 4 && cols / 4 == 64 && a.K >= 2048 && mt_total >= 3) nt = 2;
-        if (silu && nt < 2) nt = 2;
-        if (gu8 && cols % 3 == 0 && cols / 3 >= 128) nt = 3;  // 256 workgroups (backbone), 128 x 2 m-splits (code predictor)
-    } else if (silu && cols % 4 == 0 && cols / 4 >= 160 && mt_total == 4) {
-        nt = 4;                                               // backbone gate_up at full batch: 32 + 32 columns, no M split
-        if (gu8 && cols % 3 == 0 && cols / 3 >= 256) nt = 3;  // 24 columns x 256 workgroups: 14.8 vs 16.1 us
-    }
     if (g_tile_nt && epi != OMNI_EPI_RESID && (!silu || g_tile_nt >= 2) && (g_tile_nt != 3 || gu8) && cols % g_tile_nt == 0) nt = g_tile_nt;
-    const int groups = silu ? a.N / (8 * nt) : a.N / (16 * nt);
-    int splits = groups >= 160 ? 1 : (g_gemm_wgs + groups - 1) / groups;
-    // the 1024-wide gate_up (code predictor, 0.6B backbone: 128 groups of 24 columns) at 33-48 rows: three 16-row tiles, not a 32-row pair
-    // with a half-empty partner (round 5) -- the tile set of the persistent chains there, whose fourth row group then has no work in ANY
-    // stage and leaves at once instead of idling through four stages per layer to wake up for this one (B = 40: the predictor phase cost
-    // 0.25 ms MORE than at 64 rows; cp_chain.hip k_cp_chain, bb_chain.hip)
-    if (pro == 2 && gu8 && nt == 3 && groups == 128 && mt_total == 3) splits = 3;
-    if (splits > mt_total) splits = mt_total;
-    if (splits < 1) splits = 1;
-    int mt = (mt_total + splits - 1) / splits;       // 1..4
-    if (g_tile_mt) mt = g_tile_mt;
-    if (mt == 3) mt = 4;
-    if (mt > 4) mt = 4;
-    *nt_out = nt; *mt_out = mt; *splits_out = (mt_total + mt - 1) / mt;
+    skinny_tile_mt(norm, epi, a.M, a.N, nt, g_gemm_wgs, mt_out, splits_out);
+    if (g_tile_mt) {
+        *mt_out = g_tile_mt;
+        *splits_out = skinny_tile_splits(a.M, mt_out);
+    }
+    *nt_out = nt;
 }
 
 template <int PRO, int EPI>
 static int dispatch_tile(const GemmArgs& a, hipStream_t st) {
     int nt, mt, splits;
-    pick_tile(PRO == 3 ? 2 : PRO, EPI, a, &nt, &mt, &splits);      // the deferred-rstd form takes the norm-fused tiles
+    pick_tile(PRO >= 2, EPI, a, &nt, &mt, &splits);      // the deferred-rstd form takes the norm-fused tiles
 #define TILE(N_, M_) if (nt == N_ && mt == M_) return launch_gemm<M_, N_, PRO, EPI>(a, splits, st);
 #define TILE_M(N_) TILE(N_, 1) TILE(N_, 2) TILE(N_, 4)
     if constexpr (EPI == OMNI_EPI_SILU_MUL) { TILE_M(2) TILE_M(4) }

@@ -1,10 +1,15 @@
-// MFMA operand helpers shared by the skinny GEMM (gemm.hip) and the persistent code-predictor chain (cp_chain.hip):
-// the two must produce the same bits, so the arithmetic lives in one place.
+// The skinny GEMM's arithmetic, shared by its three users: gemm_skinny_kernel (gemm.hip, bf16 weights, launch per op), gemm_w8_kernel
+// (gemm_w8.hip, fp8 weights) and chain_gemm (chain_gemm.cuh, the stage of the persistent chains cp_chain / bb_chain / moe_chain).  The three
+// must produce the same bits, so the arithmetic lives in one place: the operand fragments, the slab order of the RMSNorm statistics, the
+// wave-order combine, the rstd formula, the residual epilogue's rounding points, the SiLU's, the fp8 dequantisation.  Everything here takes
+// values or an LDS pointer and returns values; the global loads and stores (plain on the launch path, coherent in the chains) stay with the caller.
 #pragma once
 #include "common.cuh"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+#define SKINNY_WAVES 8      // waves of a workgroup = K-partials of a tile: wave w owns k-steps w, w + 8, ...
 
 __device__ __forceinline__ u32x4 ld16(const uint16_t* p) { return *reinterpret_cast<const u32x4*>(p); }
 __device__ __forceinline__ u32x4 ld16_nt(const uint16_t* p) {
@@ -58,6 +63,17 @@ struct SlabOrder {
     static constexpr int CPW = 64 / XROWS, QPS = 4 / CPW, PE = 4 * QPS;
     // slab index of entry e of sub-channel `sub` of wave `wave`
     static __device__ __forceinline__ int index(int wave, int sub, int e) { return wave + 8 * ((sub * QPS + e / 4) + 4 * (e % 4)); }
+    // this thread's PE slabs of its row through `ld(p)` (a plain load on the launch path, a coherent one in the chains).  Loads are
+    // unconditional (clamped slab index, zeroed afterwards): a predicated load would force hipcc to drain every outstanding load at each wait.
+    template <class LD>
+    static __device__ __forceinline__ void gather(float (&pv)[PE], int wave, int sub, int np_in, LD ld) {
+#pragma unroll
+        for (int e = 0; e < PE; ++e) {
+            const int p = index(wave, sub, e);
+            pv[e] = ld(min(p, np_in - 1));
+            if (p >= np_in) pv[e] = 0.f;
+        }
+    }
     static __device__ __forceinline__ float reduce(const float (&pv)[PE]) {
         float q[QPS];
 #pragma unroll
@@ -87,4 +103,51 @@ __device__ __forceinline__ float silu_mul_bf16(float gate_acc, float up_acc) {
     const float up = bfround(up_acc);
     const float sl = bfround(gt / (1.0f + expf(-gt)));
     return sl * up;
+}
+
+// ---- behind the MFMA loop.  The combine area holds one 16-byte slot per (wave, tile slot, lane) = the lane's 4 accumulator registers
+// (ds_write_b128 / ds_read_b128, a quarter of the LDS instructions of [wave][reg][lane] floats): the 8 K-partials of one (slot, lane) in
+// wave order -- fixed: run-to-run deterministic, and the same bits in all three users
+__device__ __forceinline__ f32x4 combine_waves(const f32x4* lds4, int slots, int slot, int l) {
+    f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int w = 0; w < SKINNY_WAVES; ++w) sum += lds4[(w * slots + slot) * 64 + l];
+    return sum;
+}
+
+// rstd of row `ml` from the [wave][64] area of slab partials (SlabOrder::reduce of every wave): the eight partials in wave order
+__device__ __forceinline__ float row_rstd(const float* red, int ml, int K, float eps) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < SKINNY_WAVES; ++w) t += red[w * 64 + ml];
+    return 1.0f / sqrtf(t / (float)K + eps);
+}
+
+// EPI_RESID on values: r = bf16(r_old + bf16(v)) (v = the fp32 sums, bias added), or r = bf16(v) where a stream starts (`add` false); the
+// packed four, and `ss` = sum(r^2) over the row's 16 columns: the 4 lanes (l & 15) + 16 * {0..3} hold them, so every lane of a wave calls this
+struct ResidOut { u32x2 r; float ss; };
+__device__ __forceinline__ ResidOut resid_values(const float (&v)[4], u32x2 r_old, bool add) {
+    float rv[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) rv[g] = bfround(v[g]);
+    if (add) {
+        rv[0] = bfround(bf_lo(r_old[0]) + rv[0]); rv[1] = bfround(bf_hi(r_old[0]) + rv[1]);
+        rv[2] = bfround(bf_lo(r_old[1]) + rv[2]); rv[3] = bfround(bf_hi(r_old[1]) + rv[3]);
+    }
+    ResidOut o;
+    o.r = (u32x2){pack_bf2(rv[0], rv[1]), pack_bf2(rv[2], rv[3])};
+    o.ss = xor32_sum(xor16_sum(sq4_sum(rv[0], rv[1], rv[2], rv[3])));
+    return o;
+}
+
+// fp8 e4m3fn weights, dequantised in registers to the bf16 values bf16(fp8 * row scale) -- exactly the matrix a weight-only-dequantised
+// bf16 model holds (oracle: HF block on those weights): 8 bytes of one row -> the MFMA A fragment
+__device__ __forceinline__ u32x4 deq_fp8x8(u32x2 q, float s) {
+    float f[8];
+    unpack_fp8x4(q[0], f);
+    unpack_fp8x4(q[1], f + 4);
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = pack_bf2(f[2 * j] * s, f[2 * j + 1] * s);
+    return o;
 }

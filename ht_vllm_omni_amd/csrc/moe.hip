@@ -10,8 +10,7 @@
 // into MFMA A operands, the (gathered) activation rows as B operand, 8 waves splitting K, LDS combine.
 #include "common.cuh"
 #include "kernels.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "gemm_frag.cuh"      // u32x4 / u32x2, deq_fp8x8, silu_mul_bf16
 
 #define MOE_WAVES 8
 #define MOE_THREADS (MOE_WAVES * 64)
@@ -94,19 +93,7 @@ struct MoeArgs {
     int e0;                     // expert parallel: this rank holds experts [e0, e0 + gridDim.y) of the router's numbering
 };
 
-// fp8 e4m3fn weights, dequantised in registers to the bf16 values bf16(fp8 * row scale) -- exactly the matrix a
-// weight-only-dequantised bf16 model holds (oracle: HF block on those weights) -- then the same bf16 MFMA
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x4 deq_fp8x8(u32x2 q, float s) {
-    float f[8];
-    unpack_fp8x4(q[0], f);
-    unpack_fp8x4(q[1], f + 4);
-    u32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = pack_bf2(f[2 * j] * s, f[2 * j + 1] * s);
-    return o;
-}
-
+// W8: fp8 e4m3fn weights, dequantised in registers (gemm_frag.cuh deq_fp8x8), then the same bf16 MFMA
 // PHASE 1: NT = 2 tiles (16 gate + 16 up columns) -> SiLU * up; PHASE 2: NT tiles of 16 output columns, * weight
 template <int PHASE, int NT, bool W8>
 __global__ __launch_bounds__(MOE_THREADS) void moe_expert_kernel(const MoeArgs a) {
@@ -205,10 +192,7 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_expert_kernel(const MoeArgs a
             if (PHASE == 1) {
                 const int n = blockIdx.x * 16 + 4 * (l >> 4);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float gt = bfround(v[g]), up = bfround(v2[g]);
-                    o[g] = bfround(gt / (1.0f + expf(-gt))) * up;
-                }
+                for (int g = 0; g < 4; ++g) o[g] = silu_mul_bf16(v[g], v2[g]);
                 *reinterpret_cast<uint2*>(a.out + (size_t)slot * a.N + n) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
             } else {
                 const int n = (blockIdx.x * NT + j) * 16 + 4 * (l >> 4);
