@@ -56,6 +56,12 @@ class TileGemm(C.Structure):
 TILE_ACT_NONE, TILE_ACT_GELU, TILE_ACT_SILU_MUL_GU8 = 0, 1, 2
 
 
+class TileGemmFp8(C.Structure):
+    """omni_tile_gemm_fp8: one W8A8 prefill GEMM launch on the fp8 matrix path (include/omni_talker.h)."""
+    _fields_ = [("x8", vp), ("x_scale", vp), ("w8", vp), ("w_scale", vp), ("act", i32), ("out", vp), ("ldo", i32),
+                ("M", i32), ("N", i32), ("K", i32), ("tile_hint", i32)]
+
+
 class MoeAlign(C.Structure):
     """omni_moe_align_args: expert grouping of a prompt batch's (token, expert) slots on the device."""
     _fields_ = [("topk_idx", vp), ("topk_w", vp), ("T", i32), ("top_k", i32), ("e0", i32), ("E_local", i32), ("block", i32), ("r_max", i32),
@@ -129,6 +135,8 @@ SIGNATURES = {
     "omni_moe_experts_resid": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "omni_snake_beta": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "omni_gemm_tile": (i32, [C.POINTER(TileGemm), vp]),
+    "omni_quant_rows_fp8": (i32, [vp, i32, vp, vp, vp, f32, vp, vp, i32, i32, vp]),
+    "omni_gemm_tile_fp8": (i32, [C.POINTER(TileGemmFp8), vp]),
     "omni_moe_align": (i32, [C.POINTER(MoeAlign), vp]),
     "omni_moe_prefill_experts": (i32, [C.POINTER(MoePrefill), vp]),
     # include/omni_codec.h

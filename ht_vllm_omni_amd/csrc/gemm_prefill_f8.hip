@@ -1,0 +1,355 @@
+// W8A8 prefill GEMM on the fp8 matrix path of gfx950: out[M, N] = epilogue((q_x . q_w^T) * s_x[m] * s_w[n]) with both operands e4m3fn
+// bytes, v_mfma_f32_16x16x128_f8f6f4 (128 k per instruction from 32 B per lane, fp32 accumulate: twice the bf16 MFMA's rate), and the
+// row quantiser that produces q_x.  The arithmetic of `quantization: fp8` as vLLM runs it: dynamic per-token activation scales against
+// per-channel weight scales.
+//
+// Arithmetic contract (include/omni_talker.h, omni_quant_rows_fp8 / omni_gemm_tile_fp8):
+//   quantiser  s_x[m] = max(max_k |a[m, k]|, 1e-12) / 448 (fp32);  q_x[m, k] = e4m3fn(a[m, k] / s_x[m]) -- IEEE fp32 division, round to
+//              nearest even, saturating at +-448: engine.fp8_quant_rows.  With the norm prologue a = omni_rmsnorm's output row, computed
+//              by the same code (norm_row.cuh) and never stored.
+//   GEMM       acc[m, n] = sum_k q_x[m, k] q_w[n, k] (the products are exact, fp32 accumulation inside the MFMA, one MFMA per 128 k in
+//              ascending order);  y = (acc * s_x[m]) * s_w[n] in fp32;  out = bf16(y), or for the GU8 row order
+//              bf16(bf16(SiLU(bf16 gate)) * bf16 up) (omni_silu_mul's rounding points, tile_epi.cuh).
+//
+// No second copy of the weights.  W is the decode step's W8 matrix (gemm_w8.hip; the W8 fragment layout of include/omni_talker.h).  A dot
+// product does not care about the order of k as long as both operands use the same one, and in the W8 layout lane (k % 32) / 8 * 16 +
+// row % 16 of the two consecutive 1-KB blocks 2 j, 2 j + 1 of a 16-step group holds 32 bytes: 8 k of each of the k-steps {2 j, 2 j + 8,
+// 2 j + 1, 2 j + 9} -- precisely one operand of the 16x16x128 MFMA (lane = row + 16 * k-group, 8 VGPRs, 128 distinct k over the four
+// lane groups).  The K % 512 remainder lives in 512-B blocks of 8 B per lane; four consecutive ones give an operand the same way.  So a
+// 16-row tile is K / 128 CHUNKS of 2 KB, chunk c = the operand of MFMA c, and the quantiser writes the activations in the same layout
+// with tokens in place of output rows (pad rows of the last 16-row tile zero).
+//
+// Data movement.  Both operands are linear runs in HBM: a workgroup's slice (128 k) of an n-tile or m-tile is one 2-KB chunk, staged by
+// LDS-DMA as a straight copy (buffer_load_dwordx4 ... lds, two 1-KB wave instructions per chunk, no VGPR staging); tiles past N or past
+// the last live 16-row tile of x are out of the descriptor's range and read as zero.  The per-lane picking happens on the way out of
+// LDS: two ds_read_b128 (lane * 16 in each KB of a main chunk) or four ds_read_b64 (lane * 8 in each 512-B block of a remainder
+// chunk), all lane-linear and conflict-free.  Ring of NBUF slices: slice t + NBUF - 1 is staged at the top of slice t, behind the ONE
+// barrier of the slice, whose counted wait (vmcnt = the NBUF - 2 younger slices still in flight, lgkmcnt(0) for this wave's reads of the
+// buffer about to be overwritten) makes slice t visible.  A 128-deep slice of a 256 x 256 tile is 64 KB -- two fit, and each has a whole
+// slice of MFMAs (32 per wave, 2 048 cycles per SIMD) to land; the 128 x 64 tile keeps four.  A wave holds its WM x fragments (8 VGPRs
+// each) for the slice and streams its WN W fragments past them: WN * WM MFMAs per WN + WM fragment reads.
+// W is the MFMA's A operand: D[n][m], lane holds m = l & 15, n = 4 (l >> 4) + reg -- s_w belongs to the accumulator REGISTER, s_x to the
+// LANE; both are applied once, behind the loop, and the bf16 kernels' epilogue (tile_epi.cuh) stores the tile.
+// Every geometry adds k in the same order (one MFMA per chunk, chunks ascending): bit-identical outputs.
+#include <type_traits>
+
+#include "common.cuh"
+#include "gemm_frag.cuh"
+#include "kernels.h"
+#include "norm_row.cuh"
+#include "tile_epi.cuh"
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+// ---------------------------------------------------------------------------------------------------------------- row quantiser
+#define QR_ROWS_PER_BLOCK 4
+
+// byte offset of the 8 bytes (row, k0 .. k0 + 7), k0 % 8 == 0, in the W8 fragment layout of a [rows, K] matrix
+__device__ __forceinline__ size_t w8_off8(int row, int k0, int K) {
+    const int s = k0 >> 5, q = (k0 & 31) >> 3, r = row & 15, P = K >> 9;
+    const size_t tile = (size_t)(row >> 4) * 16 * K;
+    if (s < 16 * P) return tile + ((s >> 4) * 8 + (s & 7)) * 1024 + (q * 16 + r) * 16 + ((s >> 3) & 1) * 8;
+    return tile + (size_t)P * 8192 + (s - 16 * P) * 512 + (q * 16 + r) * 8;
+}
+
+// One wave per row, the row in registers (lane l: the 8-element vectors l, l + 64, ...): [norm ->] max |a| -> scale -> 8 bytes per vector.
+// Rows [M, ceil16(M)) are written as zeros (the GEMM's pad rows).
+template <int MAXV, bool NORM>
+__global__ __launch_bounds__(64 * QR_ROWS_PER_BLOCK) void quant_rows_f8_kernel(const uint16_t* __restrict__ x, int ldx, const uint16_t* __restrict__ delta,
+                                                                               uint16_t* residual, const uint16_t* __restrict__ norm_w, float eps,
+                                                                               uint8_t* __restrict__ q, float* __restrict__ scale, int M, int K) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * QR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= ((M + 15) & ~15)) return;
+    const int nvec = K >> 3;
+    uint4 pk[MAXV];                       // the row as packed bf16
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) pk[i] = make_uint4(0, 0, 0, 0);
+    if (row < M) {
+        if constexpr (NORM) {
+            const size_t ro = (size_t)row * K;
+            NormRow<MAXV> nr;
+            const float rstd = nr.load(residual ? residual + ro : x + (size_t)row * ldx, delta ? delta + ro : nullptr, residual ? residual + ro : nullptr,
+                                       false, norm_w, K, eps, lane);
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i)
+                if (lane + i * 64 < nvec) pk[i] = nr.normed(i, rstd);
+        } else {
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i)
+                if (lane + i * 64 < nvec) pk[i] = *reinterpret_cast<const uint4*>(x + (size_t)row * ldx + (lane + i * 64) * 8);
+        }
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(&pk[i]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fmaxf(fabsf(bf_lo(w[j])), fabsf(bf_hi(w[j]))));
+    }
+    amax = wave_max(amax);
+    const float s = fmaxf(amax, 1e-12f) / OMNI_FP8_MAX;
+    if (row < M && lane == 0) scale[row] = s;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int vi = lane + i * 64;
+        if (vi < nvec) {
+            const uint32_t* w = reinterpret_cast<const uint32_t*>(&pk[i]);
+            u32x2 o;
+            o[0] = pack_fp8x4(bf_lo(w[0]) / s, bf_hi(w[0]) / s, bf_lo(w[1]) / s, bf_hi(w[1]) / s);
+            o[1] = pack_fp8x4(bf_lo(w[2]) / s, bf_hi(w[2]) / s, bf_lo(w[3]) / s, bf_hi(w[3]) / s);
+            *reinterpret_cast<u32x2*>(q + w8_off8(row, vi * 8, K)) = o;
+        }
+    }
+}
+
+extern "C" int omni_quant_rows_fp8(const void* x, int ldx, const void* delta, void* residual, const void* norm_w, float eps, void* q_frag,
+                                   float* x_scale, int M, int K, void* stream) {
+    OMNI_CHECK_ARG(q_frag && x_scale && (x || residual), "omni_quant_rows_fp8: null pointer");
+    OMNI_CHECK_ARG(M >= 1 && K > 0 && K % 128 == 0, "omni_quant_rows_fp8: M=%d K=%d (M >= 1, K %% 128 == 0)", M, K);
+    OMNI_CHECK_ARG(norm_w || (!delta && !residual), "omni_quant_rows_fp8: delta / residual belong to the norm prologue (norm_w is null)");
+    OMNI_CHECK_ARG(!delta || residual, "omni_quant_rows_fp8: delta needs residual");
+    OMNI_CHECK_ARG(residual || (ldx >= K && ldx % 8 == 0), "omni_quant_rows_fp8: ldx=%d (>= K, multiple of 8)", ldx);
+    OMNI_CHECK_ARG(K <= (norm_w ? 4096 : 8192), "omni_quant_rows_fp8: K=%d too wide for a row in registers (norm prologue: 4096, plain: 8192)", K);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((((M + 15) & ~15) + QR_ROWS_PER_BLOCK - 1) / QR_ROWS_PER_BLOCK), block(64 * QR_ROWS_PER_BLOCK);
+    const int nvec = K / 8;
+#define QR_LAUNCH(V, NORM_)                                                                                                                 \
+    hipLaunchKernelGGL((quant_rows_f8_kernel<V, NORM_>), grid, block, 0, st, (const uint16_t*)x, ldx, (const uint16_t*)delta, (uint16_t*)residual, \
+                       (const uint16_t*)norm_w, eps, (uint8_t*)q_frag, x_scale, M, K)
+    if (norm_w) {
+        if (nvec <= 64 * 2) QR_LAUNCH(2, true);
+        else if (nvec <= 64 * 4) QR_LAUNCH(4, true);
+        else QR_LAUNCH(8, true);
+    } else {
+        if (nvec <= 64 * 2) QR_LAUNCH(2, false);
+        else if (nvec <= 64 * 4) QR_LAUNCH(4, false);
+        else if (nvec <= 64 * 8) QR_LAUNCH(8, false);
+        else QR_LAUNCH(16, false);
+    }
+#undef QR_LAUNCH
+    OMNI_CHECK_LAUNCH("omni_quant_rows_fp8");
+    return OMNI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- tile GEMM
+struct F8Args {
+    const uint8_t* x8; const float* xs;
+    const uint8_t* W; const float* ws;
+    uint16_t* out; int ldo;
+    int M, N, K;
+    int mblocks, nblocks, band;
+};
+
+// 8 waves as WAVES_N x (8 / WAVES_N); a wave owns WN n-tiles x WM m-tiles of 16 x 16 (tile_epi.cuh's fragment convention)
+template <int WAVES_N, int WN, int WM>
+struct F8Geom {
+    static constexpr int WAVES_M = TG_WAVES / WAVES_N;
+    static constexpr int NTILES = WAVES_N * WN, MTILES = WAVES_M * WM;
+    static constexpr int BN = NTILES * 16, BM = MTILES * 16;
+    static constexpr int SLICE = (NTILES + MTILES) * 2048;                   // one 128-deep slice of both operands
+    static constexpr int NLW = (NTILES + TG_WAVES - 1) / TG_WAVES, NLX = (MTILES + TG_WAVES - 1) / TG_WAVES;   // chunks per wave and slice
+    static constexpr int LOADS = 2 * (NLW + NLX);                            // LDS-DMA instructions per wave and slice (uniform: counted waits)
+    static constexpr bool RAGGED = NTILES % TG_WAVES != 0 || MTILES % TG_WAVES != 0;      // some waves load zeros into a spare KB
+    static constexpr int SPARE = RAGGED ? TG_WAVES * 1024 : 0;
+    static constexpr int NBUF = (TG_LDS_MAX - SPARE) / SLICE >= 4 ? 4 : (TG_LDS_MAX - SPARE) / SLICE;
+    static constexpr int EPI_BYTES = TG_WAVES * 16 * (WN * 64 + 16);
+    static constexpr int RING_BYTES = NBUF * SLICE + SPARE;
+    static constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
+    static_assert(WN % 2 == 0 && NBUF >= 2 && (NBUF - 2) * LOADS < 64 && LDS_BYTES <= TG_LDS_MAX, "geometry");
+};
+
+// one MFMA operand out of a 2-KB chunk image: a main chunk (two 1-KB blocks of 16 B per lane) or a remainder chunk (four 512-B blocks
+// of 8 B per lane); W and x chunks of one slice are of the same kind, so register e of both operands holds the same k
+template <bool MAIN>
+__device__ __forceinline__ i32x8 f8_frag(const uint8_t* chunk, int lane) {
+    if constexpr (MAIN) {
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(chunk + lane * 16), hi = *reinterpret_cast<const u32x4*>(chunk + 1024 + lane * 16);
+        return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+    } else {
+        u32x2 b[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[e] = *reinterpret_cast<const u32x2*>(chunk + e * 512 + lane * 8);
+        return i32x8{(int)b[0][0], (int)b[0][1], (int)b[1][0], (int)b[1][1], (int)b[2][0], (int)b[2][1], (int)b[3][0], (int)b[3][1]};
+    }
+}
+
+// (scale operands 0 / 0 with cbsz = blgp = 0 select the unscaled fp8 x fp8 instruction)
+__device__ __forceinline__ f32x4 f8_mfma(i32x8 a, i32x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
+}
+
+template <int WAVES_N, int WN, int WM, bool GU8>
+__global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a) {
+    using G = F8Geom<WAVES_N, WN, WM>;
+    constexpr int NTILES = G::NTILES, MTILES = G::MTILES, SLICE = G::SLICE, NLW = G::NLW, NLX = G::NLX, NBUF = G::NBUF;
+    extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wn = wave % WAVES_N, wm = wave / WAVES_N;
+    const int c = lane & 15, q = lane >> 4;
+    int n_blk, m_blk;
+    tile_block(a.band, a.mblocks, a.nblocks, n_blk, m_blk);
+    const int m0 = m_blk * G::BM, n0 = n_blk * G::BN;
+    const int nsteps = a.K >> 7;                                              // chunks = slices = MFMAs per output tile
+    const int nmain = (a.K >> 9) << 2;                                        // ... of which the whole 16-step groups
+    const size_t tile_bytes = (size_t)16 * a.K;
+
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (int)((size_t)a.N * a.K), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x8, 0, (int)((size_t)((a.M + 15) & ~15) * a.K), 0x00020000);
+
+    // ---- staging.  Slice image: W tile f at 2 f KB, x tile g at 2 (NTILES + g) KB.  Wave w copies W tiles w + 8 i and x tiles w + 8 i; a
+    // wave without an i-th tile loads zeros into its spare KB so that every wave has the same count in flight
+    unsigned wbase[NLW], xbase[NLX];
+#pragma unroll
+    for (int i = 0; i < NLW; ++i) {
+        const int f = wave + TG_WAVES * i, n16 = (n0 >> 4) + f;
+        wbase[i] = (f < NTILES && n16 * 16 < a.N) ? (unsigned)(n16 * tile_bytes + lane * 16) : TG_OOB;
+    }
+#pragma unroll
+    for (int i = 0; i < NLX; ++i) {
+        const int g = wave + TG_WAVES * i, m16 = (m0 >> 4) + g;
+        xbase[i] = (g < MTILES && m16 * 16 < a.M) ? (unsigned)(m16 * tile_bytes + lane * 16) : TG_OOB;      // 16-row tiles with a live row
+    }
+    auto copy_chunk = [&](const __amdgpu_buffer_rsrc_t& r, unsigned base, bool live, bool mine, uint8_t* img) {
+        const unsigned off = (live && base != TG_OOB) ? base : TG_OOB;
+        uint8_t* d0 = mine ? img : lds + NBUF * SLICE + wave * 1024;
+        uint8_t* d1 = mine ? img + 1024 : d0;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)d0, 16, off, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)d1, 16, off == TG_OOB ? TG_OOB : off + 1024u, 0, 0, 0);
+    };
+    auto stage = [&](int slice, int buf) {                // slices are staged in order, one call each; past the last one: zeros
+        const bool live = slice < nsteps;
+        uint8_t* img = lds + buf * SLICE;
+#pragma unroll
+        for (int i = 0; i < NLW; ++i) {
+            const int f = wave + TG_WAVES * i;
+            copy_chunk(rw, wbase[i] + (unsigned)slice * 2048u, live && wbase[i] != TG_OOB, f < NTILES, img + f * 2048);
+        }
+#pragma unroll
+        for (int i = 0; i < NLX; ++i) {
+            const int g = wave + TG_WAVES * i;
+            copy_chunk(rx, xbase[i] + (unsigned)slice * 2048u, live && xbase[i] != TG_OOB, g < MTILES, img + (NTILES + g) * 2048);
+        }
+    };
+
+    f32x4 acc[WN][WM];
+#pragma unroll
+    for (int j = 0; j < WN; ++j)
+#pragma unroll
+        for (int i = 0; i < WM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // one slice: the wave's WM x fragments stay in registers, its W fragments stream past them one ahead of the MFMAs that use them (the
+    // scheduling fences keep hipcc from reading all WN fragments first: 8 VGPRs each beside WN * WM * 4 accumulators)
+    auto mma_slice = [&](const uint8_t* img, auto main) {
+        constexpr bool MAIN = decltype(main)::value;
+        i32x8 xf[WM];
+#pragma unroll
+        for (int i = 0; i < WM; ++i) xf[i] = f8_frag<MAIN>(img + (NTILES + wm * WM + i) * 2048, lane);
+        i32x8 wf = f8_frag<MAIN>(img + (wn * WN) * 2048, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int j = 0; j < WN; ++j) {
+            i32x8 wnext = wf;
+            if (j + 1 < WN) wnext = f8_frag<MAIN>(img + (wn * WN + j + 1) * 2048, lane);
+#pragma unroll
+            for (int i = 0; i < WM; ++i) acc[j][i] = f8_mfma(wf, xf[i], acc[j][i]);
+            __builtin_amdgcn_sched_barrier(0);
+            wf = wnext;
+        }
+        __builtin_amdgcn_s_setprio(0);
+    };
+
+    // ---- main loop: one barrier per slice.  Behind it slice t is visible to every wave and every wave is done with slice t - 1, whose buffer
+    // the staging of slice t + NBUF - 1 overwrites at once.  The chunks of the whole 16-step groups first, then those of the K % 512 remainder
+    int buf = 0, sbuf = NBUF - 1;
+#pragma unroll
+    for (int s = 0; s < NBUF - 1; ++s) stage(s, s);
+    auto run = [&](int t0, int t1, auto main) {
+        for (int t = t0; t < t1; ++t) {
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((NBUF - 2) * G::LOADS) : "memory");
+            stage(t + NBUF - 1, sbuf);
+            mma_slice(lds + buf * SLICE, main);
+            buf = buf + 1 == NBUF ? 0 : buf + 1;
+            sbuf = sbuf + 1 == NBUF ? 0 : sbuf + 1;
+        }
+    };
+    run(0, nmain, std::true_type{});
+    run(nmain, nsteps, std::false_type{});
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is dead: its tail loads (zeros) landed
+
+    // ---- y = (acc * s_x[m]) * s_w[n]: the lane's m per m-tile, the register's n per n-tile.  Rows past M and columns past N are not stored
+    const int mw0 = m0 + wm * WM * 16, nw0 = n0 + wn * WN * 16;
+    float sx[WM];
+#pragma unroll
+    for (int i = 0; i < WM; ++i) {
+        const int m = mw0 + i * 16 + c;
+        sx[i] = m < a.M ? a.xs[m] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+        const int n = nw0 + j * 16 + 4 * q;
+        const f32x4 sw = n < a.N ? *reinterpret_cast<const f32x4*>(a.ws + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[j][i][e] = (acc[j][i][e] * sx[i]) * sw[e];
+    }
+    TileArgs ta{};
+    ta.out = a.out; ta.ldo = a.ldo; ta.M = a.M; ta.N = a.N;
+    tile_epilogue<WN, WM, GU8, true>(ta, acc, lds, wave, lane, mw0, nw0);
+}
+
+template <int WAVES_N, int WN, int WM, bool GU8>
+static int launch_f8(F8Args a, hipStream_t st) {
+    using G = F8Geom<WAVES_N, WN, WM>;
+    a.mblocks = (a.M + G::BM - 1) / G::BM;
+    a.nblocks = (a.N + G::BN - 1) / G::BN;
+    a.band = tile_band(a.mblocks, a.nblocks);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_f8_kernel<WAVES_N, WN, WM, GU8>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+        if (e != hipSuccess) { omni_set_error("omni_gemm_tile_fp8: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_tile_f8_kernel<WAVES_N, WN, WM, GU8>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), G::LDS_BYTES, st, a);
+    OMNI_CHECK_LAUNCH("omni_gemm_tile_fp8");
+    return OMNI_OK;
+}
+
+extern "C" int omni_gemm_tile_fp8(const omni_tile_gemm_fp8* g, void* stream) {
+    OMNI_CHECK_ARG(g && g->x8 && g->x_scale && g->w8 && g->w_scale && g->out, "omni_gemm_tile_fp8: null argument");
+    OMNI_CHECK_ARG(g->M >= 1 && g->N > 0 && g->N % 16 == 0 && g->K > 0 && g->K % 128 == 0, "omni_gemm_tile_fp8: M=%d N=%d K=%d (M >= 1, N %% 16, K %% 128)",
+                   g->M, g->N, g->K);
+    OMNI_CHECK_ARG((int64_t)g->N * g->K < (int64_t)TG_OOB && (int64_t)(g->M + 15) * g->K < (int64_t)TG_OOB, "omni_gemm_tile_fp8: an operand exceeds the 2 GB descriptor");
+    const bool gu8 = g->act == OMNI_TILE_ACT_SILU_MUL_GU8;
+    OMNI_CHECK_ARG(g->act == OMNI_TILE_ACT_NONE || gu8, "omni_gemm_tile_fp8: act=%d (none or SiLU-mul on the GU8 row order)", g->act);
+    OMNI_CHECK_ARG(g->ldo >= (gu8 ? g->N / 2 : g->N) && g->ldo % 8 == 0, "omni_gemm_tile_fp8: ldo=%d (>= output width, multiple of 8)", g->ldo);
+    OMNI_CHECK_ARG(g->tile_hint >= 0 && g->tile_hint <= 4, "omni_gemm_tile_fp8: tile_hint=%d", g->tile_hint);
+    OMNI_CHECK_ARG(g->tile_hint == 0 || g->tile_hint == 2 || g->N % 256 == 0, "omni_gemm_tile_fp8: tile_hint=%d needs N %% 256 == 0", g->tile_hint);
+    F8Args a{};
+    a.x8 = (const uint8_t*)g->x8; a.xs = g->x_scale; a.W = (const uint8_t*)g->w8; a.ws = g->w_scale;
+    a.out = (uint16_t*)g->out; a.ldo = g->ldo; a.M = g->M; a.N = g->N; a.K = g->K;
+    hipStream_t st = (hipStream_t)stream;
+    // the 128 x 64 tile where 256-column tiles do not divide N or would leave most of the 256 CUs idle (the bf16 dispatch's rule)
+    const long long big_tiles = (long long)((g->N + 255) / 256) * ((g->M + 255) / 256);
+    if (g->tile_hint == 2 || g->N % 256 != 0 || (g->tile_hint == 0 && big_tiles < 96))
+        return gu8 ? launch_f8<4, 2, 2, true>(a, st) : launch_f8<4, 2, 2, false>(a, st);
+    // 256 columns x 256 / 224 / 192 rows: one workgroup per CU, a grid runs in rounds of 256 tiles and a round costs ~ the tile's rows
+    int bm = 256;
+    if (g->tile_hint == 3) bm = 224;
+    else if (g->tile_hint == 4) bm = 192;
+    else if (g->tile_hint == 0) {
+        long long best = -1;
+        for (int cand : {256, 224, 192}) {
+            const long long tiles = (long long)((g->M + cand - 1) / cand) * (g->N / 256);
+            const long long cost = ((tiles + 255) / 256) * (cand + 16);
+            if (best < 0 || cost < best) { best = cost; bm = cand; }
+        }
+    }
+    if (bm == 224) return gu8 ? launch_f8<4, 4, 7, true>(a, st) : launch_f8<4, 4, 7, false>(a, st);
+    if (bm == 192) return gu8 ? launch_f8<4, 4, 6, true>(a, st) : launch_f8<4, 4, 6, false>(a, st);
+    return gu8 ? launch_f8<2, 8, 4, true>(a, st) : launch_f8<2, 8, 4, false>(a, st);
+}

@@ -4,6 +4,7 @@
 //   r = bf16(residual + delta);  out = w * bf16(r * rsqrt(mean(r^2) + eps))   (product rounds to bf16)
 #include "common.cuh"
 #include "kernels.h"
+#include "norm_row.cuh"
 
 #define NORM_ROWS_PER_BLOCK 4
 
@@ -16,63 +17,16 @@ __global__ __launch_bounds__(64 * NORM_ROWS_PER_BLOCK) void rmsnorm_kernel(
     const int row = blockIdx.x * NORM_ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int nvec = hidden >> 3;
-    const uint16_t* src = (residual ? residual : x) + (size_t)row * hidden;
-    float v[MAXV][8];
-    float ss = 0.f;
-    uint4 wv[MAXV];                       // norm weights: issued up front, consumed after the reduction
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int vi = lane + i * 64;
-        wv[i] = (vi < nvec) ? *reinterpret_cast<const uint4*>(w + vi * 8) : make_uint4(0, 0, 0, 0);
-    }
+    const size_t ro = (size_t)row * hidden;
+    NormRow<MAXV> nr;
+    const float rstd = nr.load((residual ? residual : x) + ro, delta ? delta + ro : nullptr, residual_out ? residual_out + ro : nullptr,
+                               residual_out && residual_out != residual, w, hidden, eps, lane);
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int vi = lane + i * 64;
         if (vi < nvec) {
-            uint4 a = *reinterpret_cast<const uint4*>(src + vi * 8);
-            const uint32_t* aw = reinterpret_cast<const uint32_t*>(&a);
-            if (delta) {
-                uint4 d = *reinterpret_cast<const uint4*>(delta + (size_t)row * hidden + vi * 8);
-                const uint32_t* dw = reinterpret_cast<const uint32_t*>(&d);
-                uint32_t o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float lo = bfround(bf_lo(aw[j]) + bf_lo(dw[j]));
-                    const float hi = bfround(bf_hi(aw[j]) + bf_hi(dw[j]));
-                    v[i][2 * j] = lo;
-                    v[i][2 * j + 1] = hi;
-                    o[j] = pack_bf2(lo, hi);
-                }
-                *reinterpret_cast<uint4*>(residual_out + (size_t)row * hidden + vi * 8) = make_uint4(o[0], o[1], o[2], o[3]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[i][2 * j] = bf_lo(aw[j]);
-                    v[i][2 * j + 1] = bf_hi(aw[j]);
-                }
-                if (residual_out && residual_out != residual)
-                    *reinterpret_cast<uint4*>(residual_out + (size_t)row * hidden + vi * 8) = a;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss += v[i][j] * v[i][j];
-        }
-    }
-    ss = wave_sum(ss);
-    const float rstd = rsqrtf(ss / (float)hidden + eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {
-            const uint32_t* wp = reinterpret_cast<const uint32_t*>(&wv[i]);
-            uint32_t o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float lo = bf_lo(wp[j]) * bfround(v[i][2 * j] * rstd);
-                const float hi = bf_hi(wp[j]) * bfround(v[i][2 * j + 1] * rstd);
-                o[j] = pack_bf2(lo, hi);
-            }
-            const uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
-            if (out && (!out_live || row < *out_live)) *reinterpret_cast<uint4*>(out + (size_t)row * hidden + vi * 8) = ov;
+            const uint4 ov = nr.normed(i, rstd);
+            if (out && (!out_live || row < *out_live)) *reinterpret_cast<uint4*>(out + ro + vi * 8) = ov;
             if (out_frag) *reinterpret_cast<uint4*>(out_frag + frag_off(row, vi * 8, hidden)) = ov;
         }
     }

@@ -192,6 +192,10 @@ class TalkerEngine:
         # and rebuild W_eff = bf16(fp8 * row scale) in registers; the bf16 W_eff copies stay for the prefill and the fall-backs, so
         # this buys decode bandwidth, not capacity (weight memory of the backbone grows by half)
         self.dense_fp8 = bool(dense_fp8)
+        # prefill_gemm="fp8": the prefill's four GEMMs on those same bytes with per-token fp8 activations (csrc/gemm_prefill_f8.hip)
+        if prefill_gemm == "fp8" and (not self.dense_fp8 or dims.moe_experts > 0 or tp_size > 1 or tp_force or not frag_layout):
+            raise ValueError("prefill_gemm='fp8' needs dense_fp8=True (a dense backbone on a single rank with frag_layout): "
+                             "it computes on the decode step's fp8 weights")
         if self.dense_fp8 and (dims.moe_experts > 0 or tp_size > 1 or tp_force or peer_allreduce is not None or not frag_layout
                                or fused_norm is False):
             raise ValueError("dense_fp8 needs a dense backbone on a single rank with frag_layout and fused_norm "
@@ -209,8 +213,10 @@ class TalkerEngine:
         self.kv_dtype = kv_dtype
         self.frag_layout = bool(frag_layout)
         # GEMMs of the all-tokens-at-once prefill: "tile" = omni_gemm_tile on the decode step's fragment-major weights (stored
-        # once); "blas" = hipBLASLt on row-major copies (another 2.8 GB at the 1.7B shape); "both" keeps both sets (tests / A-B)
-        if prefill_gemm not in ("tile", "blas", "both"):
+        # once); "blas" = hipBLASLt on row-major copies (another 2.8 GB at the 1.7B shape); "both" keeps both sets (tests / A-B);
+        # "fp8" (dense_fp8 engines) = W8A8 on omni_gemm_tile_fp8: the decode step's fp8 bytes and row scales against activations quantised
+        # per token, on the fp8 MFMA -- no weight copy of its own; such an engine can still run gemm="tile" on W_eff
+        if prefill_gemm not in ("tile", "blas", "both", "fp8"):
             raise ValueError(f"prefill_gemm={prefill_gemm!r}")
         self.prefill_gemm = prefill_gemm if self.frag_layout else "blas"
         # MoE prefill on the tile kernel: "device" = expert grouping on the device, gathered / fused expert GEMMs over the compact batch
@@ -297,13 +303,15 @@ class TalkerEngine:
                 # quantised per output row (after sharding: single rank, so the shard IS the matrix); from here on every consumer --
                 # prefill, fall-backs, the bf16 fragment-major copies in omni_layer_weights -- sees W_eff, and the decode GEMMs get the
                 # bytes in the W8 fragment layout with the scales in the kernel's row order (gate_up: GU8)
+                w8 = {}
                 for n in DENSE_NAMES:
                     q8, sc = fp8_quant_rows(sh[n])
                     sh[n] = fp8_dequant_rows(q8, sc)
                     if n == "wgu":
                         q8, sc = gu8_rows(q8), gu8_rows(sc)
-                    setattr(self._w8_layers[i], n, up(frag_shuffle_w8(q8.to(dev))).data_ptr())
-                    setattr(self._w8_layers[i], n + "_scale", up(sc.contiguous()).data_ptr())
+                    w8[n + "_w8"], w8[n + "_w8_scale"] = up(frag_shuffle_w8(q8.to(dev))), up(sc.contiguous())
+                    setattr(self._w8_layers[i], n, w8[n + "_w8"].data_ptr())
+                    setattr(self._w8_layers[i], n + "_scale", w8[n + "_w8_scale"].data_ptr())
             if self.moe_fp8:
                 # fp8 e4m3fn expert weights (BASELINE config #5): quantised per output row at load; everything downstream
                 # -- the decode kernels' in-register dequantisation, the prefill's bf16 copies, the oracle in the tests --
@@ -314,7 +322,9 @@ class TalkerEngine:
                     sh[n] = fp8_dequant_rows(q8, sc)
             # row-major copies: norms always; the dense GEMM weights only for the hipBLASLt prefill; MoE tensors for its batched path
             dense = ("wqkv", "wo", "wgu", "wdown")
-            lw = {n: up(sh[n]) for n in bb_names if self.prefill_gemm != "tile" or n not in dense}
+            lw = {n: up(sh[n]) for n in bb_names if self.prefill_gemm not in ("tile", "fp8") or n not in dense}
+            if self.dense_fp8:
+                lw.update(w8)       # the decode step's own tensors: what prefill_wide(gemm="fp8") multiplies by
             self.layer_w.append(lw)
             for n in bb_names:
                 if self.frag_layout and n in frag_names:
@@ -717,13 +727,20 @@ class TalkerEngine:
         weights): norm, q/k-norm + RoPE + KV write, causal paged attention on the native kernels; the four per-layer GEMMs
         either on omni_gemm_tile (gemm = "tile": the decode step's fragment-major weights, SiLU(gate) * up fused into the
         gate_up epilogue) or on hipBLASLt (gemm = "blas": torch.nn.functional.linear on row-major copies).  Both: bf16 in,
-        fp32 accumulate, one rounding -- the skinny kernel's convention."""
+        fp32 accumulate, one rounding -- the skinny kernel's convention.  gemm = "fp8" (dense_fp8 engines; the default of
+        prefill_gemm="fp8"): W8A8 -- every GEMM input is quantised per token (the two RMSNorms inside the quantiser: the normalised rows
+        never reach HBM) and multiplied with the decode step's fp8 weights on the fp8 MFMA (ops.quant_rows_fp8 / ops.gemm_tile_fp8)."""
         import torch.nn.functional as F
         d = self.d
-        gemm = ("tile" if self.prefill_gemm in ("tile", "both") else "blas") if gemm is None else gemm
-        if (gemm == "tile" and self.prefill_gemm == "blas") or (gemm == "blas" and self.prefill_gemm == "tile"):
-            raise L.OmniError(f"this engine was built with prefill_gemm={self.prefill_gemm!r}: no weights for the {gemm} prefill")
-        tile = gemm == "tile"
+        gemm = {"tile": "tile", "both": "tile", "fp8": "fp8"}.get(self.prefill_gemm, "blas") if gemm is None else gemm
+        if (gemm == "tile" and self.prefill_gemm == "blas") or (gemm == "blas" and self.prefill_gemm in ("tile", "fp8")) \
+                or (gemm == "fp8" and not self.dense_fp8):
+            raise L.OmniError(f"this engine was built with prefill_gemm={self.prefill_gemm!r}, dense_fp8={self.dense_fp8}: "
+                              f"no weights for the {gemm} prefill")
+        tile, f8 = gemm == "tile", gemm == "fp8"
+
+        def lin8(q_s, w, n, act=L.TILE_ACT_NONE):       # W8A8 GEMM of quantised rows against the layer's W8 matrix `n`
+            return ops.gemm_tile_fp8(q_s[0], q_s[1], w[n + "_w8"], w[n + "_w8_scale"], M=x.shape[0], act=act)
         bt = self.block_table if block_table is None else block_table
         D, hq, hkv = d.head_dim, self.hq_l, self.hkv_l
         resid = x.clone()
@@ -744,8 +761,11 @@ class TalkerEngine:
             tmp_slots = torch.arange(T, dtype=torch.int64, device=x.device)
         for l in range(d.layers):
             w = self.layer_w[l]
-            a = ops.rmsnorm(None, w["ln1"], d.eps, delta=delta, residual=resid)
-            qkv = ops.gemm_tile(a, w["wqkv_f"]) if tile else F.linear(a, w["wqkv"])
+            if f8:
+                qkv = lin8(ops.quant_rows_fp8(norm_w=w["ln1"], eps=d.eps, delta=delta, residual=resid), w, "wqkv")
+            else:
+                a = ops.rmsnorm(None, w["ln1"], d.eps, delta=delta, residual=resid)
+                qkv = ops.gemm_tile(a, w["wqkv_f"]) if tile else F.linear(a, w["wqkv"])
             kc, vc = self.kv_caches[l][0], self.kv_caches[l][1]
             ks = self.kv_scales[l] if self.kv_scales is not None else None
             if calibrate:
@@ -764,6 +784,11 @@ class TalkerEngine:
                                        block_size=self.block_size, kv_dtype=self.kv_code, k_scale=self.k_scale_l[l],
                                        v_scale=self.v_scale_l[l], k_scales=None if ks is None else ks[0],
                                        v_scales=None if ks is None else ks[1])
+            if f8:
+                o = lin8(ops.quant_rows_fp8(o), w, "wo")
+                act = lin8(ops.quant_rows_fp8(norm_w=w["ln2"], eps=d.eps, delta=o, residual=resid), w, "wgu", L.TILE_ACT_SILU_MUL_GU8)
+                delta = lin8(ops.quant_rows_fp8(act), w, "wdown")
+                continue
             o = ops.gemm_tile(o, w["wo_f"]) if tile else F.linear(o, w["wo"])
             if self.tp_path:
                 torch.distributed.all_reduce(o, group=self.tp_group)

@@ -288,6 +288,40 @@ def gemm_xnorm_w8(r_frag, partials, nparts, norm_w, w8, w_scale, eps, *, M, epil
     return out
 
 
+def quant_rows_fp8(x=None, *, norm_w=None, eps=None, delta=None, residual=None):
+    """omni_quant_rows_fp8: per-row dynamic e4m3fn quantisation (engine.fp8_quant_rows) of bf16 rows into the W8 fragment layout with
+    rows = tokens -> (q_frag uint8 [ceil16(M), K], pad rows zero; scale fp32 [M]).  Plain: x bf16 [M, K] (any row stride).  With norm_w
+    the rows are ops.rmsnorm(x, norm_w, eps, delta=, residual=)'s output, normalised and quantised in registers (the residual is updated
+    in place when delta is given; the normalised row is never stored)."""
+    src = residual if residual is not None else x
+    _chk_dev(norm_w, delta, residual, *((x,) if norm_w is not None else ()))
+    if src is None or not src.is_cuda or src.dtype != BF16 or src.dim() != 2 or src.stride(1) != 1:
+        raise L.OmniError("quant_rows_fp8: bf16 [M, K] device rows")
+    M, K = src.shape
+    q = torch.empty((M + 15) // 16 * 16, K, dtype=torch.uint8, device=src.device)
+    scale = torch.empty(M, dtype=torch.float32, device=src.device)
+    L.check(L.load().omni_quant_rows_fp8(L.ptr(x), 0 if x is None else x.stride(0), L.ptr(delta), L.ptr(residual), L.ptr(norm_w),
+                                         float(eps or 0.0), L.ptr(q), L.ptr(scale), M, K, L.current_stream()), "omni_quant_rows_fp8")
+    return q, scale
+
+
+def gemm_tile_fp8(q_frag, x_scale, w8, w_scale, *, M, act: int = L.TILE_ACT_NONE, tile_hint: int = 0):
+    """omni_gemm_tile_fp8: bf16 [M, N] = bf16(((q_x . q_w^T) * x_scale[m]) * w_scale[n]) on the fp8 MFMA.  q_frag / x_scale from
+    quant_rows_fp8; w8 uint8 [N, K] in the W8 fragment layout (engine.frag_shuffle_w8) with w_scale fp32 [N] -- the decode step's
+    buffers.  act TILE_ACT_SILU_MUL_GU8: w8 / w_scale in the GU8 row order, out [M, N / 2] = SiLU(gate) * up."""
+    _chk_dev(q_frag, x_scale, w8, w_scale)
+    N, K = w8.shape
+    if q_frag.dtype != torch.uint8 or w8.dtype != torch.uint8 or q_frag.shape != ((M + 15) // 16 * 16, K) or x_scale.numel() < M \
+            or x_scale.dtype != torch.float32 or w_scale.dtype != torch.float32 or w_scale.numel() != N:
+        raise L.OmniError("gemm_tile_fp8: q_frag uint8 [ceil16(M), K] + fp32 [M] scales against w8 uint8 [N, K] + fp32 [N] scales")
+    out = torch.empty(M, N // 2 if act == L.TILE_ACT_SILU_MUL_GU8 else N, dtype=BF16, device=w8.device)
+    g = L.TileGemmFp8()
+    g.x8, g.x_scale, g.w8, g.w_scale, g.act = q_frag.data_ptr(), x_scale.data_ptr(), w8.data_ptr(), w_scale.data_ptr(), act
+    g.out, g.ldo, g.M, g.N, g.K, g.tile_hint = out.data_ptr(), out.stride(0), M, N, K, tile_hint
+    L.check(L.load().omni_gemm_tile_fp8(C.byref(g), L.current_stream()), "omni_gemm_tile_fp8")
+    return out
+
+
 def attn_decode_fused(qkv, qnorm_w, knorm_w, positions, cos_sin, k_cache, v_cache, block_table, seq_lens, *, q_heads,
                       kv_heads, head_dim, block_size, kv_dtype, eps, k_scale=1.0, v_scale=1.0, k_scales=None, v_scales=None,
                       max_seq_len=4096, split=True):

@@ -271,6 +271,40 @@ int omni_gemm_resid_w8(const void* x_frag, const void* w8, const float* w_scale,
 int omni_gemm_xnorm_w8(const void* r, const float* partials, int nparts, const void* norm_w, float eps, const void* w8,
                        const float* w_scale, void* out, int M, int N, int K, int epilogue, int out_frag, void* stream);
 
+/* W8A8 prefill on the fp8 matrix cores (csrc/gemm_prefill_f8.hip): `quantization: fp8` as vLLM computes it for prompt tokens -- dynamic
+ * per-token activation scales against per-channel weight scales -- on the decode step's own W8 bytes (no second copy of the weights).
+ *
+ * omni_quant_rows_fp8: rows a[m] of bf16 values -> fp8 bytes + one fp32 scale per row:
+ *     s_x[m] = max(max_k |a[m, k]|, 1e-12) / 448 (fp32);   q_x[m, k] = e4m3fn(a[m, k] / s_x[m])
+ *   with IEEE fp32 division, round to nearest even, saturating at +-448 (engine.fp8_quant_rows; an all-zero row: scale 1e-12 / 448, zero
+ *   bytes).  q_frag uint8 [ceil16(M), K] receives the bytes in the W8 fragment layout above with rows = tokens; rows [M, ceil16(M)) are
+ *   written as zeros.  x_scale fp32 [M].  K % 128 == 0.
+ *     norm_w == NULL: a = x, bf16 [M, ldx] (K <= 8192); delta and residual must be NULL.
+ *     norm_w != NULL: a = the output row of omni_rmsnorm(x, delta, residual, norm_w, eps) -- the same code, the same summation order, the
+ *                     residual updated in place when delta is given -- which is never stored (K <= 4096; rows contiguous, x rows ldx).
+ *
+ * omni_gemm_tile_fp8: acc[m, n] = sum_k q_x[m, k] q_w[n, k] on v_mfma_f32_16x16x128_f8f6f4 (exact products, fp32 accumulation, one
+ *   instruction per 128 k in ascending order);  y = (acc * x_scale[m]) * w_scale[n] in fp32;
+ *     act OMNI_TILE_ACT_NONE:          out bf16 [M, ldo] = bf16(y)
+ *     act OMNI_TILE_ACT_SILU_MUL_GU8:  w8 / w_scale in the GU8 row order; out [M, N / 2] = bf16(bf16(SiLU(bf16 gate)) * bf16 up)
+ *                                      (omni_silu_mul's rounding points, as omni_gemm_tile's)
+ *   x8 = q_frag of omni_quant_rows_fp8 (pad rows zero), w8 uint8 [N, K] in the W8 fragment layout, w_scale fp32 [N] (what
+ *   omni_talker_set_dense_w8 receives).  M >= 1, N % 16 == 0, K % 128 == 0; rows >= M are not written.  No bias, GELU, residual,
+ *   snake output, conv window or groups.
+ *   tile_hint  0: automatic; 1 / 3 / 4: 256 columns x 256 / 224 / 192 rows (N % 256 == 0); 2: the 128 x 64 tile.  Every tile adds k in the
+ *              same order: bit-identical outputs.                                                                                */
+int omni_quant_rows_fp8(const void* x, int ldx, const void* delta, void* residual, const void* norm_w, float eps, void* q_frag,
+                        float* x_scale, int M, int K, void* stream);
+typedef struct omni_tile_gemm_fp8 {
+    const void* x8; const float* x_scale;
+    const void* w8; const float* w_scale;
+    int act;
+    void* out; int ldo;
+    int M, N, K;
+    int tile_hint;
+} omni_tile_gemm_fp8;
+int omni_gemm_tile_fp8(const omni_tile_gemm_fp8* g, void* stream);
+
 /* Per-head q/k RMSNorm + neox RoPE + KV-cache write with quantisation
  * (vLLM Qwen3Attention q_norm/k_norm + rotary_emb + reshape_and_cache; slot mapping built at
  * V/worker/gpu_ar_model_runner.py:239-244, passed via set_forward_context 283-292).
