@@ -75,6 +75,14 @@ class MoePrefill(C.Structure):
                 ("gu_ws", vp), ("act_ws", vp), ("y_ws", vp), ("shared", vp), ("gate_logit", vp), ("ld_gate", i32), ("out", vp)]
 
 
+class MoePrefillFp8(C.Structure):
+    """omni_moe_prefill_fp8_args: the same block on fp8 expert bytes + row scales (W8A8 on the fp8 MFMA)."""
+    _fields_ = [("x", vp), ("topk_idx", vp), ("T", i32), ("H", i32), ("I", i32), ("top_k", i32), ("E_local", i32), ("block", i32), ("r_max", i32),
+                ("block_expert", vp), ("row_token", vp), ("row_weight", vp), ("slot_row", vp), ("w_gate_up", vp), ("s_gate_up", vp),
+                ("w_down", vp), ("s_down", vp), ("x8_ws", vp), ("xs_ws", vp), ("act_ws", vp), ("a8_ws", vp), ("as_ws", vp), ("y_ws", vp),
+                ("shared", vp), ("gate_logit", vp), ("ld_gate", i32), ("out", vp)]
+
+
 class ResUnit(C.Structure):
     """omni_res_unit (include/omni_codec.h): one fused residual unit of the Code2Wav decoder."""
     _fields_ = [("s", vp), ("h", vp), ("s_next", vp), ("w1", vp), ("b1", vp), ("snake2_alpha", vp), ("snake2_inv_beta", vp),
@@ -139,6 +147,7 @@ SIGNATURES = {
     "omni_gemm_tile_fp8": (i32, [C.POINTER(TileGemmFp8), vp]),
     "omni_moe_align": (i32, [C.POINTER(MoeAlign), vp]),
     "omni_moe_prefill_experts": (i32, [C.POINTER(MoePrefill), vp]),
+    "omni_moe_prefill_experts_fp8": (i32, [C.POINTER(MoePrefillFp8), vp]),
     # include/omni_codec.h
     "omni_codec_rvq_embed": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp]),
     "omni_codec_rmsnorm": (i32, [vp, i32, vp, f32, vp, i32, i32, vp]),

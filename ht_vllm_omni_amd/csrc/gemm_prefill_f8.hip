@@ -31,6 +31,27 @@
 // W is the MFMA's A operand: D[n][m], lane holds m = l & 15, n = 4 (l >> 4) + reg -- s_w belongs to the accumulator REGISTER, s_x to the
 // LANE; both are applied once, behind the loop, and the bf16 kernels' epilogue (tile_epi.cuh) stores the tile.
 // Every geometry adds k in the same order (one MFMA per chunk, chunks ascending): bit-identical outputs.
+//
+// MoE prefill on fp8 expert weights (MOE != 0 instantiations; entry point omni_moe_prefill_experts_fp8 in moe_prefill.hip): the grouped
+// gate_up and down GEMMs over the compact expert-sorted batch of omni_moe_align (one m block = 64 or 256 rows of ONE expert), on the bytes
+// and row scales the decode step's omni_moe_experts_ex reads -- no copy of the expert weights.
+//   W  An expert matrix is frag_shuffle(q8): one byte per weight in the bf16 fragment order (frag_off, common.cuh), i.e. a 16-row tile is
+//      K / 32 consecutive 512-B blocks of 8 B per lane (q * 16 + r) -- w8_off8 with P = 0: EVERY chunk is a remainder chunk, whatever K is
+//      (no main part is derived from K >> 9).  Chunk c = k-steps 4 c .. 4 c + 3, a straight 2-KB LDS-DMA copy, read back with four
+//      ds_read_b64: register pair e of lane (q, r) holds k = 128 c + 32 e + 8 q + j.  Expert base = expert * N * K bytes, scales [E, N].
+//   x  LDS-DMA moves 16 B per lane, not 8, so the activations are quantised into a layout of their own (quant_rows_f8_kernel<.., TOK>):
+//      token-major [rows, K] with k permuted inside every 128-k chunk -- byte 32 q + 8 e + j of the chunk holds k = 32 e + 8 q + j.  Lane
+//      (c, q) fetches the two 16-B pieces at byte 32 q of its SOURCE row (gate_up: row_token[batch row], the gather; down: the act row as
+//      it lies); the two instructions leave the image f8_frag<true> reads, registers [e0 e1 | e2 e3]: the same k as W's, pair for pair.
+//      Rows with row_token < 0 and rows past the descriptor read as zero.  No VGPR staging on either operand.
+//   Arithmetic contract (include/omni_talker.h, omni_moe_prefill_experts_fp8):
+//      gate_up  g = (acc * s_x[token]) * s_w[n] in fp32 for gate and for up, act = bf16(bf16(SiLU(bf16 g_gate)) * bf16 g_up)
+//               (omni_silu_mul's three roundings, as MOE_GU_FUSED of gemm_prefill.hip); n block nb covers columns [nb BN/2, + BN/2) of gate
+//               AND of up, a wave's first WN / 2 n-tiles being gate and the second WN / 2 the same columns of up;
+//      down     y = bf16(bf16((acc * s_a[row]) * s_w[n]) * row_weight[row]) (MOE_DOWN's two roundings);
+//      k order  one MFMA per chunk, ascending, in both geometries (128 x 64 for 64-row blocks, 256 x 256 for 256-row blocks).
+//   The act quantiser skips the rows of blocks without an expert (never written by gate_up; the down GEMM leaves those blocks at once);
+//   pad rows inside an expert's block are zeros: zero bytes, scale 1e-12 / 448.
 #include <type_traits>
 
 #include "common.cuh"
@@ -54,13 +75,18 @@ __device__ __forceinline__ size_t w8_off8(int row, int k0, int K) {
 
 // One wave per row, the row in registers (lane l: the 8-element vectors l, l + 64, ...): [norm ->] max |a| -> scale -> 8 bytes per vector.
 // Rows [M, ceil16(M)) are written as zeros (the GEMM's pad rows).
-template <int MAXV, bool NORM>
+// TOK: the MoE prefill's token-major layout (file header) instead -- no pad rows, and with block_expert the rows of blocks (`block` rows
+// each) that no expert owns are left alone.
+template <int MAXV, bool NORM, bool TOK = false>
 __global__ __launch_bounds__(64 * QR_ROWS_PER_BLOCK) void quant_rows_f8_kernel(const uint16_t* __restrict__ x, int ldx, const uint16_t* __restrict__ delta,
                                                                                uint16_t* residual, const uint16_t* __restrict__ norm_w, float eps,
-                                                                               uint8_t* __restrict__ q, float* __restrict__ scale, int M, int K) {
+                                                                               uint8_t* __restrict__ q, float* __restrict__ scale, int M, int K,
+                                                                               const int32_t* __restrict__ block_expert = nullptr, int block = 1) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * QR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (row >= ((M + 15) & ~15)) return;
+    if (row >= (TOK ? M : ((M + 15) & ~15))) return;
+    if constexpr (TOK)
+        if (block_expert && block_expert[row / block] < 0) return;
     const int nvec = K >> 3;
     uint4 pk[MAXV];                       // the row as packed bf16
 #pragma unroll
@@ -98,7 +124,9 @@ __global__ __launch_bounds__(64 * QR_ROWS_PER_BLOCK) void quant_rows_f8_kernel(c
             u32x2 o;
             o[0] = pack_fp8x4(bf_lo(w[0]) / s, bf_hi(w[0]) / s, bf_lo(w[1]) / s, bf_hi(w[1]) / s);
             o[1] = pack_fp8x4(bf_lo(w[2]) / s, bf_hi(w[2]) / s, bf_lo(w[3]) / s, bf_hi(w[3]) / s);
-            *reinterpret_cast<u32x2*>(q + w8_off8(row, vi * 8, K)) = o;
+            // TOK: vector vi = k 8 vi .. + 7 = (chunk vi >> 4, e = (vi >> 2) & 3, q = vi & 3) -> byte 32 q + 8 e of the row's chunk
+            const size_t off = TOK ? (size_t)row * K + (vi >> 4) * 128 + (vi & 3) * 32 + ((vi >> 2) & 3) * 8 : w8_off8(row, vi * 8, K);
+            *reinterpret_cast<u32x2*>(q + off) = o;
         }
     }
 }
@@ -132,6 +160,23 @@ extern "C" int omni_quant_rows_fp8(const void* x, int ldx, const void* delta, vo
     return OMNI_OK;
 }
 
+int k_quant_rows_f8_tok(const void* x, int ldx, void* q, float* scale, int M, int K, const int32_t* block_expert, int block, void* stream) {
+    OMNI_CHECK_ARG(x && q && scale && M >= 1 && K > 0 && K % 128 == 0 && K <= 8192 && ldx >= K && ldx % 8 == 0 && block >= 1,
+                   "omni_moe_prefill_experts_fp8: quantiser M=%d K=%d ldx=%d (K %% 128 == 0, K <= 8192)", M, K, ldx);
+    const dim3 grid((M + QR_ROWS_PER_BLOCK - 1) / QR_ROWS_PER_BLOCK), block_dim(64 * QR_ROWS_PER_BLOCK);
+    const int nvec = K / 8;
+#define QR_LAUNCH(V)                                                                                                                         \
+    hipLaunchKernelGGL((quant_rows_f8_kernel<V, false, true>), grid, block_dim, 0, (hipStream_t)stream, (const uint16_t*)x, ldx, (const uint16_t*)nullptr, \
+                       (uint16_t*)nullptr, (const uint16_t*)nullptr, 0.f, (uint8_t*)q, scale, M, K, block_expert, block)
+    if (nvec <= 64 * 2) QR_LAUNCH(2);
+    else if (nvec <= 64 * 4) QR_LAUNCH(4);
+    else if (nvec <= 64 * 8) QR_LAUNCH(8);
+    else QR_LAUNCH(16);
+#undef QR_LAUNCH
+    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts_fp8(quantiser)");
+    return OMNI_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- tile GEMM
 struct F8Args {
     const uint8_t* x8; const float* xs;
@@ -139,6 +184,11 @@ struct F8Args {
     uint16_t* out; int ldo;
     int M, N, K;
     int mblocks, nblocks, band;
+    // MOE != 0 (file header): x8 = x_rows token-major rows, xs per source row; W / ws per expert ([E, N, K] bytes, [E, N] scales); the maps of
+    // omni_moe_align -- m block b belongs to expert block_expert[b] (< 0: none, the workgroup leaves), batch row r reads token row_token[r]
+    // (gate_up; < 0: zeros) and carries the routing weight row_weight[r] (down)
+    int x_rows;
+    const int32_t* block_expert; const int32_t* row_token; const uint16_t* row_weight;
 };
 
 // 8 waves as WAVES_N x (8 / WAVES_N); a wave owns WN n-tiles x WM m-tiles of 16 x 16 (tile_epi.cuh's fragment convention)
@@ -179,7 +229,7 @@ __device__ __forceinline__ f32x4 f8_mfma(i32x8 a, i32x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
 }
 
-template <int WAVES_N, int WN, int WM, bool GU8>
+template <int WAVES_N, int WN, int WM, bool GU8, int MOE = 0>
 __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a) {
     using G = F8Geom<WAVES_N, WN, WM>;
     constexpr int NTILES = G::NTILES, MTILES = G::MTILES, SLICE = G::SLICE, NLW = G::NLW, NLX = G::NLX, NBUF = G::NBUF;
@@ -191,32 +241,56 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
     int n_blk, m_blk;
     tile_block(a.band, a.mblocks, a.nblocks, n_blk, m_blk);
     const int m0 = m_blk * G::BM, n0 = n_blk * G::BN;
+    const uint8_t* W = a.W;
+    const float* ws = a.ws;
+    if constexpr (MOE != 0) {
+        const int expert = a.block_expert[m_blk];                             // uniform: one expert per m block
+        if (expert < 0) return;                                               // past the last expert's rows
+        W += (size_t)expert * a.N * a.K;
+        ws += (size_t)expert * a.N;
+    }
     const int nsteps = a.K >> 7;                                              // chunks = slices = MFMAs per output tile
-    const int nmain = (a.K >> 9) << 2;                                        // ... of which the whole 16-step groups
+    const int nmain = (a.K >> 9) << 2;                                        // ... of which the whole 16-step groups (MOE: unused, none)
     const size_t tile_bytes = (size_t)16 * a.K;
 
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (int)((size_t)a.N * a.K), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x8, 0, (int)((size_t)((a.M + 15) & ~15) * a.K), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, (int)((size_t)a.N * a.K), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x8, 0, (int)((size_t)(MOE != 0 ? a.x_rows : ((a.M + 15) & ~15)) * a.K), 0x00020000);
 
     // ---- staging.  Slice image: W tile f at 2 f KB, x tile g at 2 (NTILES + g) KB.  Wave w copies W tiles w + 8 i and x tiles w + 8 i; a
     // wave without an i-th tile loads zeros into its spare KB so that every wave has the same count in flight
     unsigned wbase[NLW], xbase[NLX];
 #pragma unroll
     for (int i = 0; i < NLW; ++i) {
-        const int f = wave + TG_WAVES * i, n16 = (n0 >> 4) + f;
-        wbase[i] = (f < NTILES && n16 * 16 < a.N) ? (unsigned)(n16 * tile_bytes + lane * 16) : TG_OOB;
+        const int f = wave + TG_WAVES * i;
+        int n16 = (n0 >> 4) + f;
+        bool in_n = n16 * 16 < a.N;
+        if constexpr (MOE == MOE_GU_FUSED) {                                  // tile f = n-tile j of wave column f / WN: gate (j < WN / 2) or up
+            constexpr int HN = WN / 2;
+            const int j = f % WN;
+            const int col16 = n_blk * (NTILES / 2) + (f / WN) * HN + j % HN;  // 16-column tile of the [rows, I] output
+            in_n = col16 * 32 < a.N;
+            n16 = (j >= HN ? a.N >> 5 : 0) + col16;
+        }
+        wbase[i] = (f < NTILES && in_n) ? (unsigned)(n16 * tile_bytes + lane * 16) : TG_OOB;
     }
 #pragma unroll
     for (int i = 0; i < NLX; ++i) {
         const int g = wave + TG_WAVES * i, m16 = (m0 >> 4) + g;
         xbase[i] = (g < MTILES && m16 * 16 < a.M) ? (unsigned)(m16 * tile_bytes + lane * 16) : TG_OOB;      // 16-row tiles with a live row
+        if constexpr (MOE != 0) {                                             // per-lane source row: lane (c, q) fetches bytes [32 q, + 32) of its chunk
+            int src = g < MTILES ? m0 + g * 16 + c : -1;
+            if constexpr (MOE == MOE_GU_FUSED)
+                if (src >= 0) src = a.row_token[src];                         // the gather; < 0: a padding row
+            xbase[i] = (src >= 0 && src < a.x_rows) ? (unsigned)((size_t)src * a.K + 32 * q) : TG_OOB;
+        }
     }
-    auto copy_chunk = [&](const __amdgpu_buffer_rsrc_t& r, unsigned base, bool live, bool mine, uint8_t* img) {
+    // the second 1-KB piece of a chunk lies `second` bytes behind the first in the source: 1 KB in a fragment layout, 16 B in a token-major row
+    auto copy_chunk = [&](const __amdgpu_buffer_rsrc_t& r, unsigned base, bool live, bool mine, uint8_t* img, unsigned second = 1024u) {
         const unsigned off = (live && base != TG_OOB) ? base : TG_OOB;
         uint8_t* d0 = mine ? img : lds + NBUF * SLICE + wave * 1024;
         uint8_t* d1 = mine ? img + 1024 : d0;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)d0, 16, off, 0, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)d1, 16, off == TG_OOB ? TG_OOB : off + 1024u, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)d1, 16, off == TG_OOB ? TG_OOB : off + second, 0, 0, 0);
     };
     auto stage = [&](int slice, int buf) {                // slices are staged in order, one call each; past the last one: zeros
         const bool live = slice < nsteps;
@@ -229,7 +303,8 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
 #pragma unroll
         for (int i = 0; i < NLX; ++i) {
             const int g = wave + TG_WAVES * i;
-            copy_chunk(rx, xbase[i] + (unsigned)slice * 2048u, live && xbase[i] != TG_OOB, g < MTILES, img + (NTILES + g) * 2048);
+            if constexpr (MOE != 0) copy_chunk(rx, xbase[i] + (unsigned)slice * 128u, live && xbase[i] != TG_OOB, g < MTILES, img + (NTILES + g) * 2048, 16u);
+            else copy_chunk(rx, xbase[i] + (unsigned)slice * 2048u, live && xbase[i] != TG_OOB, g < MTILES, img + (NTILES + g) * 2048);
         }
     };
 
@@ -243,16 +318,17 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
     // scheduling fences keep hipcc from reading all WN fragments first: 8 VGPRs each beside WN * WM * 4 accumulators)
     auto mma_slice = [&](const uint8_t* img, auto main) {
         constexpr bool MAIN = decltype(main)::value;
+        constexpr bool XMAIN = MOE != 0 || MAIN, WMAIN = MOE == 0 && MAIN;   // MOE: x images of two 16-B pieces against W remainder chunks
         i32x8 xf[WM];
 #pragma unroll
-        for (int i = 0; i < WM; ++i) xf[i] = f8_frag<MAIN>(img + (NTILES + wm * WM + i) * 2048, lane);
-        i32x8 wf = f8_frag<MAIN>(img + (wn * WN) * 2048, lane);
+        for (int i = 0; i < WM; ++i) xf[i] = f8_frag<XMAIN>(img + (NTILES + wm * WM + i) * 2048, lane);
+        i32x8 wf = f8_frag<WMAIN>(img + (wn * WN) * 2048, lane);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < WN; ++j) {
             i32x8 wnext = wf;
-            if (j + 1 < WN) wnext = f8_frag<MAIN>(img + (wn * WN + j + 1) * 2048, lane);
+            if (j + 1 < WN) wnext = f8_frag<WMAIN>(img + (wn * WN + j + 1) * 2048, lane);
 #pragma unroll
             for (int i = 0; i < WM; ++i) acc[j][i] = f8_mfma(wf, xf[i], acc[j][i]);
             __builtin_amdgcn_sched_barrier(0);
@@ -275,22 +351,35 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
             sbuf = sbuf + 1 == NBUF ? 0 : sbuf + 1;
         }
     };
-    run(0, nmain, std::true_type{});
-    run(nmain, nsteps, std::false_type{});
+    if constexpr (MOE != 0) {
+        run(0, nsteps, std::false_type{});
+    } else {
+        run(0, nmain, std::true_type{});
+        run(nmain, nsteps, std::false_type{});
+    }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is dead: its tail loads (zeros) landed
 
     // ---- y = (acc * s_x[m]) * s_w[n]: the lane's m per m-tile, the register's n per n-tile.  Rows past M and columns past N are not stored
-    const int mw0 = m0 + wm * WM * 16, nw0 = n0 + wn * WN * 16;
+    // (MOE: s_x belongs to the SOURCE row -- the token of a gathered row; the fused gate_up's n-tile j is gate (j < WN / 2) or up of column tile j % (WN / 2))
+    constexpr int HN = WN / 2;
+    const int mw0 = m0 + wm * WM * 16, nw0 = MOE == MOE_GU_FUSED ? n_blk * (G::BN / 2) + wn * HN * 16 : n0 + wn * WN * 16;
     float sx[WM];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-        const int m = mw0 + i * 16 + c;
-        sx[i] = m < a.M ? a.xs[m] : 0.f;
+        int m = mw0 + i * 16 + c;
+        if constexpr (MOE == MOE_GU_FUSED) m = a.row_token[m];
+        sx[i] = (m >= 0 && m < (MOE != 0 ? a.x_rows : a.M)) ? a.xs[m] : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
-        const int n = nw0 + j * 16 + 4 * q;
-        const f32x4 sw = n < a.N ? *reinterpret_cast<const f32x4*>(a.ws + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+        int n = nw0 + j * 16 + 4 * q;
+        bool in_n = n < a.N;
+        if constexpr (MOE == MOE_GU_FUSED) {
+            const int col = nw0 + (j % HN) * 16 + 4 * q;
+            in_n = col < (a.N >> 1);
+            n = (j >= HN ? a.N >> 1 : 0) + col;
+        }
+        const f32x4 sw = in_n ? *reinterpret_cast<const f32x4*>(ws + n) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -298,7 +387,30 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
     }
     TileArgs ta{};
     ta.out = a.out; ta.ldo = a.ldo; ta.M = a.M; ta.N = a.N;
-    tile_epilogue<WN, WM, GU8, true>(ta, acc, lds, wave, lane, mw0, nw0);
+    if constexpr (MOE == MOE_GU_FUSED) {
+        f32x4 o[HN][WM];
+#pragma unroll
+        for (int j = 0; j < HN; ++j)
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[j][i][e] = silu_mul_bf16(acc[j][i][e], acc[HN + j][i][e]);
+        ta.N = a.N >> 1;                                                      // the output's width
+        tile_epilogue<HN, WM, false, true>(ta, o, lds, wave, lane, mw0, nw0);
+    } else if constexpr (MOE == MOE_DOWN) {
+        // the two rounding points of y = bf16(acc) followed by y * weight on bf16 tensors; the lane holds row (lane & 15) of m-tile i
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+            const float wgt = bf2f(a.row_weight[mw0 + i * 16 + c]);
+#pragma unroll
+            for (int j = 0; j < WN; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[j][i][e] = bfround(acc[j][i][e]) * wgt;
+        }
+        tile_epilogue<WN, WM, false, true>(ta, acc, lds, wave, lane, mw0, nw0);
+    } else {
+        tile_epilogue<WN, WM, GU8, true>(ta, acc, lds, wave, lane, mw0, nw0);
+    }
 }
 
 template <int WAVES_N, int WN, int WM, bool GU8>
@@ -352,4 +464,44 @@ extern "C" int omni_gemm_tile_fp8(const omni_tile_gemm_fp8* g, void* stream) {
     if (bm == 224) return gu8 ? launch_f8<4, 4, 7, true>(a, st) : launch_f8<4, 4, 7, false>(a, st);
     if (bm == 192) return gu8 ? launch_f8<4, 4, 6, true>(a, st) : launch_f8<4, 4, 6, false>(a, st);
     return gu8 ? launch_f8<2, 8, 4, true>(a, st) : launch_f8<2, 8, 4, false>(a, st);
+}
+
+// ---- the MoE prefill's expert GEMMs on fp8 weights over the compact batch (entry point: moe_prefill.hip).  Two block heights, the same k
+// order: 64 rows = <4, 2, 2> (128 columns; gate_up: 64 gate + 64 up), 256 rows = <2, 8, 4> (256 columns; gate_up: 128 + 128).
+template <int WAVES_N, int WN, int WM, int MOE>
+static int launch_f8_moe(F8Args a, hipStream_t st) {
+    using G = F8Geom<WAVES_N, WN, WM>;
+    a.mblocks = a.M / G::BM;
+    a.nblocks = MOE == MOE_GU_FUSED ? (a.N / 2) / (G::BN / 2) : (a.N + G::BN - 1) / G::BN;
+    a.band = tile_band(a.mblocks, a.nblocks);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_f8_kernel<WAVES_N, WN, WM, false, MOE>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+        if (e != hipSuccess) { omni_set_error("omni_moe_prefill_experts_fp8: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_tile_f8_kernel<WAVES_N, WN, WM, false, MOE>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), G::LDS_BYTES, st, a);
+    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts_fp8");
+    return OMNI_OK;
+}
+
+int k_moe_tile_gemm_f8(int mode, int block, const void* x8, const float* x_scale, int x_rows, const void* w8, const float* w_scale, int experts,
+                       const int32_t* block_expert, const int32_t* row_token, const void* row_weight, void* out, int ldo, int rows, int N, int K,
+                       void* stream) {
+    OMNI_CHECK_ARG(x8 && x_scale && w8 && w_scale && block_expert && out && (mode == MOE_DOWN ? row_weight != nullptr : row_token != nullptr),
+                   "omni_moe_prefill_experts_fp8: null argument");
+    OMNI_CHECK_ARG(mode == MOE_GU_FUSED || mode == MOE_DOWN, "omni_moe_prefill_experts_fp8: mode=%d", mode);
+    OMNI_CHECK_ARG((block == 64 || block == 256) && rows > 0 && rows % block == 0, "omni_moe_prefill_experts_fp8: block=%d rows=%d", block, rows);
+    OMNI_CHECK_ARG(N > 0 && N % 128 == 0 && (mode != MOE_GU_FUSED || N % 256 == 0) && K > 0 && K % 128 == 0 && ldo % 8 == 0 && experts >= 1,
+                   "omni_moe_prefill_experts_fp8: N=%d K=%d ldo=%d", N, K, ldo);
+    OMNI_CHECK_ARG(x_rows > 0 && (int64_t)x_rows * K < (int64_t)TG_OOB && (int64_t)N * K < (int64_t)TG_OOB, "omni_moe_prefill_experts_fp8: an operand exceeds the 2 GB descriptor");
+    OMNI_CHECK_ARG(mode != MOE_DOWN || x_rows >= rows, "omni_moe_prefill_experts_fp8: act rows");
+    F8Args a{};
+    a.x8 = (const uint8_t*)x8; a.xs = x_scale; a.x_rows = x_rows; a.W = (const uint8_t*)w8; a.ws = w_scale;
+    a.out = (uint16_t*)out; a.ldo = ldo; a.M = rows; a.N = N; a.K = K;
+    a.block_expert = block_expert; a.row_token = row_token; a.row_weight = (const uint16_t*)row_weight;
+    hipStream_t st = (hipStream_t)stream;
+    if (block == 64) return mode == MOE_GU_FUSED ? launch_f8_moe<4, 2, 2, MOE_GU_FUSED>(a, st) : launch_f8_moe<4, 2, 2, MOE_DOWN>(a, st);
+    return mode == MOE_GU_FUSED ? launch_f8_moe<2, 8, 4, MOE_GU_FUSED>(a, st) : launch_f8_moe<2, 8, 4, MOE_DOWN>(a, st);
 }

@@ -146,3 +146,12 @@ bool k_moe_tile_fused_ok(int block, int I);
 int k_moe_tile_gemm(int mode, int block, const void* x, int64_t x_rows, int ldx, const void* w, int64_t w_expert_elems, int experts,
                     const int32_t* block_expert, const int32_t* row_token, const void* row_weight, void* out, int ldo, int rows, int N, int K,
                     void* stream);
+// ... and their fp8 siblings (gemm_prefill_f8.hip, MOE instantiations of gemm_tile_f8_kernel): w8 = [experts, N, K] bytes, each matrix
+// frag_shuffle(q8) (the decode step's moe_fp8 tensors), w_scale fp32 [experts, N]; x8 / x_scale from k_quant_rows_f8_tok (token-major rows with
+// k permuted inside every 128-k chunk, x_rows of them; one scale per row).  MOE_GU_FUSED and MOE_DOWN only: N % 128 == 0, K % 128 == 0.
+// k_quant_rows_f8_tok: omni_quant_rows_fp8's arithmetic on x bf16 [M, ldx]; with block_expert the rows of blocks (`block` rows each) that
+// no expert owns are neither read nor written.
+int k_quant_rows_f8_tok(const void* x, int ldx, void* q, float* scale, int M, int K, const int32_t* block_expert, int block, void* stream);
+int k_moe_tile_gemm_f8(int mode, int block, const void* x8, const float* x_scale, int x_rows, const void* w8, const float* w_scale, int experts,
+                       const int32_t* block_expert, const int32_t* row_token, const void* row_weight, void* out, int ldo, int rows, int N, int K,
+                       void* stream);

@@ -212,3 +212,32 @@ extern "C" int omni_moe_prefill_experts(const omni_moe_prefill_args* g, void* st
     OMNI_CHECK_LAUNCH("omni_moe_prefill_experts(combine)");
     return OMNI_OK;
 }
+
+// The same block on the decode step's fp8 expert bytes (gemm_prefill_f8.hip: the fp8 MFMA, W8A8): quantise the token rows once, gathered
+// gate_up GEMM, quantise the act rows of the blocks an expert owns, down GEMM, the unchanged combine.  No host read.
+extern "C" int omni_moe_prefill_experts_fp8(const omni_moe_prefill_fp8_args* g, void* stream) {
+    OMNI_CHECK_ARG(g && g->x && g->topk_idx && g->block_expert && g->row_token && g->row_weight && g->slot_row && g->w_gate_up && g->s_gate_up &&
+                   g->w_down && g->s_down && g->x8_ws && g->xs_ws && g->act_ws && g->a8_ws && g->as_ws && g->y_ws && g->out,
+                   "omni_moe_prefill_experts_fp8: null argument");
+    OMNI_CHECK_ARG(g->T >= 1 && g->top_k >= 1 && g->top_k <= MP_MAXK && g->E_local >= 1 && g->E_local <= MP_MAXE,
+                   "omni_moe_prefill_experts_fp8: T=%d top_k=%d E_local=%d", g->T, g->top_k, g->E_local);
+    OMNI_CHECK_ARG(g->H > 0 && g->H % 128 == 0 && g->I > 0 && g->I % 128 == 0, "omni_moe_prefill_experts_fp8: H=%d I=%d (H %% 128, I %% 128)", g->H, g->I);
+    OMNI_CHECK_ARG(g->block == 64 || g->block == 256, "omni_moe_prefill_experts_fp8: block=%d (64 | 256)", g->block);
+    OMNI_CHECK_ARG(g->r_max == moe_r_max(g->T, g->top_k, g->E_local, g->block), "omni_moe_prefill_experts_fp8: r_max=%d does not belong to these sizes", g->r_max);
+    OMNI_CHECK_ARG(!g->shared || (g->gate_logit && g->ld_gate >= 1), "omni_moe_prefill_experts_fp8: shared expert output without its gate logits");
+    const int H = g->H, I = g->I, R = g->r_max;
+    int rc = k_quant_rows_f8_tok(g->x, H, g->x8_ws, g->xs_ws, g->T, H, nullptr, 1, stream);
+    if (rc != OMNI_OK) return rc;
+    rc = k_moe_tile_gemm_f8(MOE_GU_FUSED, g->block, g->x8_ws, g->xs_ws, g->T, g->w_gate_up, g->s_gate_up, g->E_local, g->block_expert, g->row_token,
+                            nullptr, g->act_ws, I, R, 2 * I, H, stream);
+    if (rc != OMNI_OK) return rc;
+    rc = k_quant_rows_f8_tok(g->act_ws, I, g->a8_ws, g->as_ws, R, I, g->block_expert, g->block, stream);
+    if (rc != OMNI_OK) return rc;
+    rc = k_moe_tile_gemm_f8(MOE_DOWN, g->block, g->a8_ws, g->as_ws, R, g->w_down, g->s_down, g->E_local, g->block_expert, nullptr, g->row_weight,
+                            g->y_ws, H, R, H, I, stream);
+    if (rc != OMNI_OK) return rc;
+    hipLaunchKernelGGL(moe_prefill_combine_kernel, dim3(g->T), dim3(128), 0, (hipStream_t)stream, (const uint16_t*)g->y_ws, g->topk_idx,
+                       g->slot_row, (const uint16_t*)g->shared, (const uint16_t*)g->gate_logit, g->ld_gate, (uint16_t*)g->out, g->top_k, H);
+    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts_fp8(combine)");
+    return OMNI_OK;
+}

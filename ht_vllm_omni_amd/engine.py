@@ -193,9 +193,18 @@ class TalkerEngine:
         # this buys decode bandwidth, not capacity (weight memory of the backbone grows by half)
         self.dense_fp8 = bool(dense_fp8)
         # prefill_gemm="fp8": the prefill's four GEMMs on those same bytes with per-token fp8 activations (csrc/gemm_prefill_f8.hip)
-        if prefill_gemm == "fp8" and (not self.dense_fp8 or dims.moe_experts > 0 or tp_size > 1 or tp_force or not frag_layout):
-            raise ValueError("prefill_gemm='fp8' needs dense_fp8=True (a dense backbone on a single rank with frag_layout): "
-                             "it computes on the decode step's fp8 weights")
+        # ... and on an MoE model with moe_fp8=True: the routed experts' two grouped GEMMs on the decode step's fp8 expert bytes (the MOE
+        # instantiations of that file; ops.moe_prefill_experts), attention projections / router / shared expert on the bf16 tile GEMM
+        self.moe_prefill_fp8 = prefill_gemm == "fp8" and dims.moe_experts > 0 and bool(moe_fp8) and not self.dense_fp8
+        if self.moe_prefill_fp8:
+            if tp_size > 1 or tp_force or not frag_layout or moe_dispatch != "device":
+                raise ValueError("prefill_gemm='fp8' on an MoE model needs a single rank with frag_layout and moe_dispatch='device'")
+            if dims.hidden % 128 or dims.moe_inter % 128:
+                raise ValueError(f"prefill_gemm='fp8' on an MoE model needs hidden % 128 == 0 and moe_inter % 128 == 0 "
+                                 f"(hidden={dims.hidden}, moe_inter={dims.moe_inter})")
+        elif prefill_gemm == "fp8" and (not self.dense_fp8 or dims.moe_experts > 0 or tp_size > 1 or tp_force or not frag_layout):
+            raise ValueError("prefill_gemm='fp8' needs dense_fp8=True (a dense backbone on a single rank with frag_layout) or, on an MoE "
+                             "model, moe_fp8=True: it computes on the decode step's fp8 weights")
         if self.dense_fp8 and (dims.moe_experts > 0 or tp_size > 1 or tp_force or peer_allreduce is not None or not frag_layout
                                or fused_norm is False):
             raise ValueError("dense_fp8 needs a dense backbone on a single rank with frag_layout and fused_norm "
@@ -319,10 +328,12 @@ class TalkerEngine:
                 for n in ("moe_gate_up", "moe_down"):
                     q8, sc = fp8_quant_rows(sh[n])
                     sh[n + "_q8"], sh[n + "_scale"] = q8, sc
-                    sh[n] = fp8_dequant_rows(q8, sc)
+                    if not self.moe_prefill_fp8:        # (that engine's prefill multiplies the bytes themselves: no bf16 expert copy at all)
+                        sh[n] = fp8_dequant_rows(q8, sc)
             # row-major copies: norms always; the dense GEMM weights only for the hipBLASLt prefill; MoE tensors for its batched path
             dense = ("wqkv", "wo", "wgu", "wdown")
-            lw = {n: up(sh[n]) for n in bb_names if self.prefill_gemm not in ("tile", "fp8") or n not in dense}
+            lw = {n: up(sh[n]) for n in bb_names if (self.prefill_gemm not in ("tile", "fp8") or n not in dense)
+                  and not (self.moe_prefill_fp8 and n in ("moe_gate_up", "moe_down"))}
             if self.dense_fp8:
                 lw.update(w8)       # the decode step's own tensors: what prefill_wide(gemm="fp8") multiplies by
             self.layer_w.append(lw)
@@ -331,7 +342,10 @@ class TalkerEngine:
                     # fragment-major copy for the native GEMMs (per expert for MoE; dense gate_up interleaved by 8)
                     if self.moe_fp8 and n in ("moe_gate_up", "moe_down"):
                         t_ = up(frag_shuffle(sh[n + "_q8"]))            # same element order, one byte per weight
-                        setattr(self._layers[i], n + "_scale", up(sh[n + "_scale"]).data_ptr())
+                        sc_ = up(sh[n + "_scale"])
+                        setattr(self._layers[i], n + "_scale", sc_.data_ptr())
+                        if self.moe_prefill_fp8:                        # the decode step's own tensors: what the fp8 prefill multiplies by
+                            lw[n + "_f"], lw[n + "_scale"] = t_, sc_
                     else:
                         src = lw[n] if n in lw else sh[n].to(dev)       # shuffled on the device; the row-major temporary is dropped
                         t_ = up(gu8_shuffle(src) if n == "wgu" else frag_shuffle(src))
@@ -343,12 +357,13 @@ class TalkerEngine:
                 else:
                     t_ = lw[n]
                 setattr(self._layers[i], n, t_.data_ptr())
-            if d.moe_experts > 0 and self.prefill_gemm in ("tile", "both"):
+            if d.moe_experts > 0 and self.prefill_gemm in ("tile", "both", "fp8"):
                 # the prefill's grouped omni_gemm_tile reads the decode step's fragment-major expert matrices (bf16 experts: the
                 # very same tensors; fp8 experts: one dequantised fragment-major copy -- the tile kernel's LDS-DMA path moves
                 # bf16 fragments); router / shared-expert gate as fragment-major too (the gate's single row padded to one tile)
                 for n in ("moe_gate_up", "moe_down"):
-                    lw[n + "_f"] = up(frag_shuffle(lw[n])) if self.moe_fp8 else self._frag_keep[(i, n)]
+                    if not self.moe_prefill_fp8:
+                        lw[n + "_f"] = up(frag_shuffle(lw[n])) if self.moe_fp8 else self._frag_keep[(i, n)]
                 lw["moe_router_f"] = up(frag_shuffle(lw["moe_router"]))
                 if self.moe_shared_l > 0:
                     for n in ("moe_shared_gate_up", "moe_shared_down"):
@@ -361,7 +376,7 @@ class TalkerEngine:
                 # torch.bmm on the transposed VIEW of [E, N, K] faults on this ROCm build at the talker's shapes
                 # (scripts/diag_bmm.py); they replace the row-major expert copies, which nothing else reads
                 for n in ("moe_gate_up", "moe_down"):
-                    rm = lw.pop(n)
+                    rm = lw.pop(n, None)
                     if self.prefill_gemm in ("blas", "both"):
                         lw[n + "_t"] = rm.transpose(1, 2).contiguous()
                     del rm
@@ -729,10 +744,15 @@ class TalkerEngine:
         gate_up epilogue) or on hipBLASLt (gemm = "blas": torch.nn.functional.linear on row-major copies).  Both: bf16 in,
         fp32 accumulate, one rounding -- the skinny kernel's convention.  gemm = "fp8" (dense_fp8 engines; the default of
         prefill_gemm="fp8"): W8A8 -- every GEMM input is quantised per token (the two RMSNorms inside the quantiser: the normalised rows
-        never reach HBM) and multiplied with the decode step's fp8 weights on the fp8 MFMA (ops.quant_rows_fp8 / ops.gemm_tile_fp8)."""
+        never reach HBM) and multiplied with the decode step's fp8 weights on the fp8 MFMA (ops.quant_rows_fp8 / ops.gemm_tile_fp8).
+        On an MoE engine built with moe_fp8=True, prefill_gemm="fp8" the default is the tile pass with the routed experts' two grouped
+        GEMMs as W8A8 on the decode step's fp8 expert bytes (_moe_mlp_tile -> ops.moe_prefill_experts); attention projections, router
+        and shared expert stay on the bf16 tile GEMM."""
         import torch.nn.functional as F
         d = self.d
         gemm = {"tile": "tile", "both": "tile", "fp8": "fp8"}.get(self.prefill_gemm, "blas") if gemm is None else gemm
+        if self.moe_prefill_fp8 and gemm == "fp8":
+            gemm = "tile"       # an MoE engine's fp8 prefill: the routed experts on fp8 (_moe_mlp_tile), everything else on the bf16 tile GEMM
         if (gemm == "tile" and self.prefill_gemm == "blas") or (gemm == "blas" and self.prefill_gemm in ("tile", "fp8")) \
                 or (gemm == "fp8" and not self.dense_fp8):
             raise L.OmniError(f"this engine was built with prefill_gemm={self.prefill_gemm!r}, dense_fp8={self.dense_fp8}: "
@@ -873,8 +893,10 @@ class TalkerEngine:
             if with_shared:
                 sh = ops.gemm_tile(ops.silu_mul(ops.gemm_tile(a, w["moe_shared_gate_up_f"])), w["moe_shared_down_f"])
                 gate = ops.gemm_tile(a, w["moe_shared_gate_f"])
+            # (a prefill_gemm="fp8" engine holds the decode step's fp8 bytes and row scales here: the op takes its W8A8 path)
             return ops.moe_prefill_experts(a, idx, wts, w["moe_gate_up_f"], w["moe_down_f"], E=d.moe_experts, e0=self.moe_e0, shared=sh,
-                                           gate_logit=gate, block=self.moe_block)
+                                           gate_logit=gate, block=self.moe_block, gate_up_scale=w.get("moe_gate_up_scale"),
+                                           down_scale=w.get("moe_down_scale"))
         order, dst, wts_s, counts, cap = self._moe_group_slots(idx, wts, T)
         rows = counts.to(torch.int32)
         xb = torch.empty(E * cap, H, dtype=BF16, device=a.device)       # rows past an expert's count are never read

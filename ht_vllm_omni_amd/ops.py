@@ -147,37 +147,63 @@ def moe_align(idx, wts, E, block=64, e0=0, n_local=None):
     return row_start, block_expert, row_token, row_weight, slot_row
 
 
-def moe_prefill_experts(x, idx, wts, gate_up_f, down_f, *, E, e0=0, shared=None, gate_logit=None, block=None):
+def moe_prefill_experts(x, idx, wts, gate_up_f, down_f, *, E, e0=0, shared=None, gate_logit=None, block=None, gate_up_scale=None,
+                        down_scale=None, return_stages=False):
     """Routed experts + combine of the sparse-MoE MLP over T >= 1 rows with no host read (omni_moe_align + omni_moe_prefill_experts):
     x bf16 [T, H], routing idx / wts [T, k] over E experts, gate_up_f [n_local, 2I, H] / down_f [n_local, H, I] fragment-major per
     expert = experts [e0, e0 + n_local); shared bf16 [T, H] + gate_logit bf16 [T, >= 1] (column 0): the sigmoid-gated shared expert's
     term.  block: 64 | 256 rows per expert block (None: from the mean rows per expert).  Scratch comes from torch's allocator (a captured
-    graph owns it).  Returns bf16 [T, H]."""
-    _chk_dev(x, idx, wts, gate_up_f, down_f, shared)
+    graph owns it).  Returns bf16 [T, H].
+    uint8 gate_up_f / down_f (the decode step's fp8 expert bytes, engine.frag_shuffle of fp8_quant_rows' bytes) with gate_up_scale fp32
+    [n_local, 2I] / down_scale fp32 [n_local, H]: W8A8 on the fp8 MFMA (omni_moe_prefill_experts_fp8; H % 128 == 0, I % 128 == 0).
+    return_stages: (out, stages) with the workspaces of the call -- act, y, the alignment maps and, on fp8 weights, x8 / x_scale and
+    act8 / act_scale (token-major rows, k permuted inside every 128-k chunk: include/omni_talker.h)."""
+    _chk_dev(x, idx, wts, gate_up_f, down_f, shared, gate_up_scale, down_scale)
     T, H = x.shape
     k = idx.shape[1]
     n_local, two_i = gate_up_f.shape[0], gate_up_f.shape[1]
     I = two_i // 2
+    f8 = gate_up_f.dtype == torch.uint8
+    if f8 != (down_f.dtype == torch.uint8) or (not f8 and gate_up_f.dtype != BF16):
+        raise L.OmniError("moe_prefill_experts: gate_up_f and down_f are both bf16 or both uint8 (fp8 bytes)")
+    if f8:
+        if H % 128 or I % 128:
+            raise L.OmniError(f"moe_prefill_experts: fp8 experts need H % 128 == 0 and I % 128 == 0 (H={H}, I={I})")
+        if any(s is None or s.dtype != torch.float32 or not s.is_contiguous() for s in (gate_up_scale, down_scale)) \
+                or gate_up_scale.shape != (n_local, two_i) or down_scale.shape != (n_local, H) or not x.is_contiguous():
+            raise L.OmniError("moe_prefill_experts: fp8 experts need gate_up_scale fp32 [n_local, 2I] and down_scale fp32 [n_local, H]")
     block = moe_block_height(T, k, n_local) if block is None else block
     row_start, block_expert, row_token, row_weight, slot_row = moe_align(idx, wts, E, block, e0, n_local)
     r_max = row_token.numel()
     dev = x.device
-    g = L.MoePrefill()
+    g = L.MoePrefillFp8() if f8 else L.MoePrefill()
     g.x, g.topk_idx = x.data_ptr(), idx.data_ptr()
     g.T, g.H, g.I, g.top_k, g.E_local, g.block, g.r_max = T, H, I, k, n_local, block, r_max
     g.block_expert, g.row_token, g.row_weight, g.slot_row = block_expert.data_ptr(), row_token.data_ptr(), row_weight.data_ptr(), slot_row.data_ptr()
     g.w_gate_up, g.w_down = gate_up_f.data_ptr(), down_f.data_ptr()
     act = torch.empty(r_max, I, dtype=BF16, device=dev)
     y = torch.empty(r_max, H, dtype=BF16, device=dev)
-    gu = torch.empty(r_max, two_i, dtype=BF16, device=dev) if I % (64 if block == 64 else 128) else None      # widths the fused epilogue does not divide
     out = torch.empty(T, H, dtype=BF16, device=dev)
-    g.gu_ws, g.act_ws, g.y_ws, g.out = L.ptr(gu), act.data_ptr(), y.data_ptr(), out.data_ptr()
+    g.act_ws, g.y_ws, g.out = act.data_ptr(), y.data_ptr(), out.data_ptr()
+    stages = dict(act=act, y=y, row_start=row_start, block_expert=block_expert, row_token=row_token, row_weight=row_weight, slot_row=slot_row)
+    if f8:
+        x8, a8 = torch.empty(T, H, dtype=torch.uint8, device=dev), torch.empty(r_max, I, dtype=torch.uint8, device=dev)
+        xs, a_s = torch.empty(T, dtype=torch.float32, device=dev), torch.empty(r_max, dtype=torch.float32, device=dev)
+        g.s_gate_up, g.s_down = gate_up_scale.data_ptr(), down_scale.data_ptr()
+        g.x8_ws, g.xs_ws, g.a8_ws, g.as_ws = x8.data_ptr(), xs.data_ptr(), a8.data_ptr(), a_s.data_ptr()
+        stages.update(x8=x8, x_scale=xs, act8=a8, act_scale=a_s)
+    else:
+        gu = torch.empty(r_max, two_i, dtype=BF16, device=dev) if I % (64 if block == 64 else 128) else None      # widths the fused epilogue does not divide
+        g.gu_ws = L.ptr(gu)
     if shared is not None:
         if gate_logit is None or gate_logit.dtype != BF16 or gate_logit.stride(1) != 1 or gate_logit.shape[0] != T or not gate_logit.is_cuda:
             raise L.OmniError("moe_prefill_experts: shared needs gate_logit bf16 [T, >= 1]")
         g.shared, g.gate_logit, g.ld_gate = shared.data_ptr(), gate_logit.data_ptr(), gate_logit.stride(0)
-    L.check(L.load().omni_moe_prefill_experts(C.byref(g), L.current_stream()), "omni_moe_prefill_experts")
-    return out
+    if f8:
+        L.check(L.load().omni_moe_prefill_experts_fp8(C.byref(g), L.current_stream()), "omni_moe_prefill_experts_fp8")
+    else:
+        L.check(L.load().omni_moe_prefill_experts(C.byref(g), L.current_stream()), "omni_moe_prefill_experts")
+    return (out, stages) if return_stages else out
 
 
 def _frag(w):
@@ -188,11 +214,13 @@ def _frag(w):
     return w.reshape(-1, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(-1, K)
 
 
-def moe_block_prefill(x, w, top_k, norm_topk_prob=False, block=None):
+def moe_block_prefill(x, w, top_k, norm_topk_prob=False, block=None, return_stages=False):
     """moe_block for any T >= 1 (the decode op stops at 64 rows): router, routed experts and shared expert on the tile kernel, expert
     grouping on the device -- no host read, capturable in a graph.  Same weight dict as moe_block; the row-major router / shared-expert
     matrices are brought to fragment-major here unless the dict already holds them as router_f, shared_gate_up_f, shared_down_f,
-    shared_gate_f ([16, H]: the gate's row padded to one tile).  Returns (out bf16 [T, H], idx, wts)."""
+    shared_gate_f ([16, H]: the gate's row padded to one tile).  A dict whose gate_up_f / down_f are uint8 holds their row scales as
+    gate_up_scale / down_scale (moe_prefill_experts' fp8 path).  Returns (out bf16 [T, H], idx, wts); return_stages: out = (out, stages)
+    with the shared expert's term as stages["shared"] / ["gate_logit"]."""
     E = w["gate_up_f"].shape[0]
     f = lambda n: w[n + "_f"] if w.get(n + "_f") is not None else _frag(w[n])      # noqa: E731
     logits = gemm_tile(x, f("router"))
@@ -204,7 +232,10 @@ def moe_block_prefill(x, w, top_k, norm_topk_prob=False, block=None):
     if sgu is not None and sgu.shape[0] > 0:
         shared = gemm_tile(silu_mul(gemm_tile(x, f("shared_gate_up"))), f("shared_down"))
         gate = gemm_tile(x, f("shared_gate"))
-    out = moe_prefill_experts(x, idx, wts, w["gate_up_f"], w["down_f"], E=E, shared=shared, gate_logit=gate, block=block)
+    out = moe_prefill_experts(x, idx, wts, w["gate_up_f"], w["down_f"], E=E, shared=shared, gate_logit=gate, block=block,
+                              gate_up_scale=w.get("gate_up_scale"), down_scale=w.get("down_scale"), return_stages=return_stages)
+    if return_stages:
+        out[1].update(shared=shared, gate_logit=gate)
     return out, idx, wts
 
 

@@ -305,6 +305,30 @@ typedef struct omni_tile_gemm_fp8 {
 } omni_tile_gemm_fp8;
 int omni_gemm_tile_fp8(const omni_tile_gemm_fp8* g, void* stream);
 
+/* omni_moe_prefill_experts_fp8: omni_moe_prefill_experts on the decode step's fp8 expert weights, W8A8 on the fp8 MFMA (the MOE
+ * instantiations of csrc/gemm_prefill_f8.hip) -- no bf16 copy of the experts.  Same maps (omni_moe_align), same combine.
+ *   w_gate_up uint8 [E_local, 2I, H] = [gate rows | up rows], w_down uint8 [E_local, H, I]: e4m3fn bytes, each expert matrix in the
+ *   fragment-major element order (what omni_moe_experts_ex reads); s_gate_up fp32 [E_local, 2I], s_down fp32 [E_local, H] row scales.
+ *   x8_ws / xs_ws  the token rows quantised as omni_quant_rows_fp8 does (same scales, same bytes) into uint8 [T, H], token-major with k
+ *                  permuted inside every 128-k chunk: byte 32 q + 8 e + j of a chunk holds k = 32 e + 8 q + j; fp32 [T] scales.
+ *   act [r_max, I] = bf16(bf16(SiLU(bf16 g_gate)) * bf16 g_up),  g = (acc * xs[token]) * s_gate_up[e][n] in fp32,
+ *                  acc = sum_k q_x[token, k] q_w[e][n, k]: exact products, fp32 accumulation, one MFMA per 128 k in ascending order.
+ *                  Padding rows of an expert's blocks are zeros; rows of blocks without an expert are not written.
+ *   a8_ws / as_ws  act quantised the same way, uint8 [r_max, I] + fp32 [r_max] (rows of blocks without an expert: not written)
+ *   y [r_max, H]   = bf16(bf16((acc * as[row]) * s_down[e][n]) * row_weight[row])
+ *   out            as omni_moe_prefill_experts.
+ * H % 128 == 0, I % 128 == 0, top_k <= 8; block 64 | 256 (bit-identical outputs).                                                  */
+typedef struct omni_moe_prefill_fp8_args {
+    const void* x; const int32_t* topk_idx;
+    int T, H, I, top_k, E_local, block, r_max;
+    const int32_t* block_expert; const int32_t* row_token; const void* row_weight; const int32_t* slot_row;
+    const void* w_gate_up; const float* s_gate_up; const void* w_down; const float* s_down;
+    void* x8_ws; float* xs_ws; void* act_ws; void* a8_ws; float* as_ws; void* y_ws;
+    const void* shared; const void* gate_logit; int ld_gate;
+    void* out;
+} omni_moe_prefill_fp8_args;
+int omni_moe_prefill_experts_fp8(const omni_moe_prefill_fp8_args* a, void* stream);
+
 /* Per-head q/k RMSNorm + neox RoPE + KV-cache write with quantisation
  * (vLLM Qwen3Attention q_norm/k_norm + rotary_emb + reshape_and_cache; slot mapping built at
  * V/worker/gpu_ar_model_runner.py:239-244, passed via set_forward_context 283-292).
