@@ -163,6 +163,7 @@ SIGNATURES = {
     "omni_gemm_resid_w8": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
     "omni_gemm_xnorm_w8": (i32, [vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "omni_talker_set_dense_w8": (i32, [vp, C.POINTER(DenseW8Layer)]),
+    "omni_talker_set_dense_w8_chain": (i32, [vp, i32]),
     "omni_attn_decode_fused": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
                                      f32, f32, f32, i32, vp]),
     "omni_qknorm_rope_kvwrite": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, f32, f32, vp]),

@@ -22,6 +22,9 @@
 
 struct BbArgs {
     const uint16_t *wo, *ln2, *wgu, *wdown, *ln1_next, *wqkv_next;      // *_next == NULL: last layer, no qkv stage
+    // the W8 instantiations (omni_talker_set_dense_w8_chain): wo / wgu / wdown / wqkv_next point at fp8 bytes in the W8 fragment layout, these at
+    // their fp32 row scales (wgu in the GU8 row order); lm_head stays bf16
+    const float *so, *sgu, *sdown, *sqkv_next;
     int pf;                             // cross-stage weight prefetch (0: every stage fetches its own slice at its entry)
     const uint16_t* attn;               // fragment-major [64][2048]: the attention launch's output
     uint16_t* resid; float* part;       // fragment-major residual stream [64][2048] + sum(r^2) slabs [128][64]
@@ -57,11 +60,16 @@ struct BbArgs {
 // stage grid, two VIRTUAL workgroups each, stage by stage (a virtual workgroup's stage needs only stages that every physical workgroup has
 // already run or will run before it waits again: no cycle) -- two such launches of two processes fit the chip side by side, which is how the
 // cross-process exchange is tested on one GPU (tests/test_gpu_tp.py) and how a co-located second engine keeps its backbone chain
+// W8: the four backbone stages read fp8 weights (chain_gemm WSRC 4), every stage's whole slice ahead of its flags -- at one byte per weight
+// gate_up's slice is 48 registers, not the 96 that kept it in the activation ring on bf16 (GUW0); same tiles, workgroup -> tile maps and ring
+// depths as the bf16 stage set, the head stage stays on the bf16 lm_head.  Single rank, full grid, every reduction width a multiple of 512.
 template <int KO, int KH, int KI, int GU_G, int DN_G, int QK_G, bool PF, bool GU1P = true, bool GUW0 = false, bool DEFER = true, int WNT = 0, bool HEAD = false,
-          bool AR = false, bool HALF = false>
+          bool AR = false, bool HALF = false, bool W8 = false>
 __global__ __launch_bounds__(CH_THREADS) void bb_chain_kernel(const BbArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     static_assert(!PF || (!AR && !HALF), "the cross-stage prefetch arm is a single-rank, full-grid experiment");
+    static_assert(!W8 || (!PF && !AR && !HALF && DEFER && KO % 2 == 0 && KH % 2 == 0 && KI % 2 == 0),
+                  "the W8 stage set: single rank, full grid, deferred rstd, whole 512-wide groups");
     uint32_t e0 = 0;
     if constexpr (AR) e0 = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.ar_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     ChainGate g;
@@ -120,26 +128,28 @@ __global__ __launch_bounds__(CH_THREADS) void bb_chain_kernel(const BbArgs a) {
     constexpr int NT1 = (WNT & 1) ? OMNI_AUX_NT : 0, NT2 = (WNT & 2) ? OMNI_AUX_NT : 0;
     // the four stages of (virtual) workgroup WG_ behind gate G_
 #define BB_O(WG_, G_)                                                                                                                                   \
-    chain_gemm<2, 1, KO, 0, OMNI_EPI_RESID, 0, 0, ChainNoPrefetch, false, 64, NT2, AR>(a.wo, nullptr, a.attn, nullptr, 0, a.resid, 0, a.part, a.B, H, a.eps,    \
+    chain_gemm<2, 1, KO, 0, OMNI_EPI_RESID, 0, W8 ? 4 : 0, ChainNoPrefetch, false, 64, NT2, AR>(a.wo, nullptr, a.attn, nullptr, 0, a.resid, 0, a.part, a.B, H, a.eps, \
                                                                                        (WG_) % nc_h, (WG_) / nc_h, lds, G_, false, 0x1001, a.stamps, nullptr,  \
-                                                                                       ChainNoPrefetch(), nullptr, nullptr, 0.f, nullptr, &a.ar_o, e0 + 1u)
+                                                                                       ChainNoPrefetch(), nullptr, nullptr, 0.f, nullptr, &a.ar_o, e0 + 1u, a.so)
 #define BB_GU(WG_, G_)                                                                                                                                  \
     do {                                                                                                                                                \
         if ((WG_) < nc_gu)                                                                                                                              \
-            chain_gemm<4, 3, KH, DEFER ? 3 : 2, OMNI_EPI_SILU_MUL_GU8, GU_G, GUW0 ? 0 : 1, ChainNoPrefetch, GU1P, 64, NT1>(                              \
-                a.wgu, a.ln2, a.resid, a.part, H / 16, a.act, 0, nullptr, a.B, I, a.eps, WG_, 0, lds, G_, true, 0x1002, a.stamps);                        \
+            chain_gemm<4, 3, KH, DEFER ? 3 : 2, OMNI_EPI_SILU_MUL_GU8, GU_G, W8 ? 4 : (GUW0 ? 0 : 1), ChainNoPrefetch, GU1P, 64, NT1>(                   \
+                a.wgu, a.ln2, a.resid, a.part, H / 16, a.act, 0, nullptr, a.B, I, a.eps, WG_, 0, lds, G_, true, 0x1002, a.stamps, nullptr,                \
+                ChainNoPrefetch(), nullptr, nullptr, 0.f, nullptr, nullptr, 0, a.sgu);                                                                    \
         else                                                                                                                                            \
             chain_gate_skip(G_);                                                                                                                        \
     } while (0)
 #define BB_DN(WG_, G_)                                                                                                                                  \
-    chain_gemm<2, 1, KI, 0, OMNI_EPI_RESID, DN_G, 0, ChainNoPrefetch, false, 64, NT2, AR>(a.wdown, nullptr, a.act, nullptr, 0, a.resid, 0, a.part, a.B, H,       \
+    chain_gemm<2, 1, KI, 0, OMNI_EPI_RESID, DN_G, W8 ? 4 : 0, ChainNoPrefetch, false, 64, NT2, AR>(a.wdown, nullptr, a.act, nullptr, 0, a.resid, 0, a.part, a.B, H, \
                                                                                           a.eps, (WG_) % nc_h, (WG_) / nc_h, lds, G_, true, 0x1003, a.stamps,   \
                                                                                           nullptr, ChainNoPrefetch(), nullptr, nullptr, 0.f, nullptr, &a.ar_dn,  \
-                                                                                          e0 + 2u)
+                                                                                          e0 + 2u, a.sdown)
 #define BB_QK(WG_, G_)                                                                                                                                  \
-    chain_gemm<2, 2, KH, DEFER ? 3 : 2, OMNI_EPI_BF16, QK_G, 0, ChainNoPrefetch, false, 64, NT2>(a.wqkv_next, a.ln1_next, a.resid, a.part, H / 16, a.qkv, NQ,    \
+    chain_gemm<2, 2, KH, DEFER ? 3 : 2, OMNI_EPI_BF16, QK_G, W8 ? 4 : 0, ChainNoPrefetch, false, 64, NT2>(a.wqkv_next, a.ln1_next, a.resid, a.part, H / 16, a.qkv, NQ, \
                                                                                                  nullptr, a.B, NQ, a.eps, (WG_) % nc_q, (WG_) / nc_q, lds, G_,   \
-                                                                                                 true, 0x1004, a.stamps)
+                                                                                                 true, 0x1004, a.stamps, nullptr, ChainNoPrefetch(), nullptr,    \
+                                                                                                 nullptr, 0.f, nullptr, nullptr, 0, a.sqkv_next)
     if constexpr (HALF) {
         static_assert(!HALF || !HEAD, "the half grid has no head stage (a tensor-parallel rank's lm_head stays its own launch)");
         ChainGate g2;
@@ -223,9 +233,13 @@ __global__ __launch_bounds__(CH_THREADS) void bb_chain_small_kernel(const BbArgs
 // ---- the 1.7B shape at 1-32 rows (round 4): the launch path's tiles at those batch sizes -- 16-row tiles for qkv / o_proj / down_proj
 // (128 column tiles x 2 row tiles), gate_up on 16 rows x 24 columns up to 16 rows and 32 x 24 above (the rstd summation order follows the
 // rows per tile: same bits as the launch path).  33-48 rows: bb_chain_kernel (the 64-row stage set).
-template <int KO, int KH, int KI, int GU_MT, bool HEAD = false>
+// W8: as bb_chain_kernel's -- the four backbone stages on fp8 weights, whole slices ahead of the flags
+template <int KO, int KH, int KI, int GU_MT, bool HEAD = false, bool W8 = false>
 __global__ __launch_bounds__(CH_THREADS) void bb_chain_b32_kernel(const BbArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    static_assert(!W8 || (KO % 2 == 0 && KH % 2 == 0 && KI % 2 == 0), "the W8 stage set: whole 512-wide groups");
+    constexpr int WS_ = W8 ? 4 : 0, WS_GU = W8 ? 4 : 1;
+#define BB_W8_TAIL(S_) nullptr, ChainNoPrefetch(), nullptr, nullptr, 0.f, nullptr, nullptr, 0, S_
     ChainGate g;
     chain_gate_init(g, a.flags, a.err);
     g.dom = 8;
@@ -233,18 +247,19 @@ __global__ __launch_bounds__(CH_THREADS) void bb_chain_b32_kernel(const BbArgs a
     const int wg = blockIdx.x;
     const int H = a.H, I = a.I, NQ = a.NQ;
     const int nc_h = H >> 4, nc_gu = I / 24, nc_q = NQ >> 5;        // 16-row tiles: two row tiles of each column tile cover the 32 rows
-    chain_gemm<1, 1, KO, 0, OMNI_EPI_RESID, 0>(a.wo, nullptr, a.attn, nullptr, 0, a.resid, 0, a.part, a.B, H, a.eps, wg % nc_h, wg / nc_h, lds, g, false, 0x1001,
-                                               a.stamps);
+    chain_gemm<1, 1, KO, 0, OMNI_EPI_RESID, 0, WS_>(a.wo, nullptr, a.attn, nullptr, 0, a.resid, 0, a.part, a.B, H, a.eps, wg % nc_h, wg / nc_h, lds, g, false, 0x1001,
+                                                    a.stamps, BB_W8_TAIL(a.so));
     if (wg < nc_gu)
-        chain_gemm<GU_MT, 3, KH, 3, OMNI_EPI_SILU_MUL_GU8, 2, 1>(a.wgu, a.ln2, a.resid, a.part, H / 16, a.act, 0, nullptr, a.B, I, a.eps, wg, 0, lds, g, true, 0x1002,
-                                                                 a.stamps);
+        chain_gemm<GU_MT, 3, KH, 3, OMNI_EPI_SILU_MUL_GU8, 2, WS_GU>(a.wgu, a.ln2, a.resid, a.part, H / 16, a.act, 0, nullptr, a.B, I, a.eps, wg, 0, lds, g, true, 0x1002,
+                                                                     a.stamps, BB_W8_TAIL(a.sgu));
     else
         chain_gate_skip(g);
-    chain_gemm<1, 1, KI, 0, OMNI_EPI_RESID, 4>(a.wdown, nullptr, a.act, nullptr, 0, a.resid, 0, a.part, a.B, H, a.eps, wg % nc_h, wg / nc_h, lds, g, true, 0x1003,
-                                               a.stamps);
+    chain_gemm<1, 1, KI, 0, OMNI_EPI_RESID, 4, WS_>(a.wdown, nullptr, a.act, nullptr, 0, a.resid, 0, a.part, a.B, H, a.eps, wg % nc_h, wg / nc_h, lds, g, true, 0x1003,
+                                                    a.stamps, BB_W8_TAIL(a.sdown));
     if (a.wqkv_next)
-        chain_gemm<1, 2, KH, 3, OMNI_EPI_BF16, 4>(a.wqkv_next, a.ln1_next, a.resid, a.part, H / 16, a.qkv, NQ, nullptr, a.B, NQ, a.eps, wg % nc_q, wg / nc_q, lds, g,
-                                                  true, 0x1004, a.stamps);
+        chain_gemm<1, 2, KH, 3, OMNI_EPI_BF16, 4, WS_>(a.wqkv_next, a.ln1_next, a.resid, a.part, H / 16, a.qkv, NQ, nullptr, a.B, NQ, a.eps, wg % nc_q, wg / nc_q, lds, g,
+                                                       true, 0x1004, a.stamps, BB_W8_TAIL(a.sqkv_next));
+#undef BB_W8_TAIL
     else if (HEAD && a.lm_head) {
         const int nc_v = a.V >> 5;
         chain_gemm<1, 2, KH, 2, OMNI_EPI_F32_BF16RND, 4>(a.lm_head, a.final_norm, a.resid, a.part, H / 16, a.logits, a.V, nullptr, a.B, a.V, a.eps, wg % nc_v,
@@ -301,36 +316,53 @@ bool k_bb_chain_supported(const omni_talker_desc& d, int B, const omni_ar_peers*
 bool k_bb_chain_small(const omni_talker_desc& d) {
     return d.hidden == 1024 && d.inter == 3072 && d.q_heads * 128 == 2048 && (d.q_heads + 2 * d.kv_heads) * 128 == 4096;
 }
+// the W8 stage sets: a single rank's full grid on a BB_SHAPES triple whose three reduction widths are whole 512-wide groups of the W8 fragment
+// layout (the 8-B-per-lane remainder of K % 512 has no stage: such a shape stays launch per op); the 0.6B stage set has no W8 form
+bool k_bb_chain_w8_supported(const omni_talker_desc& d, int B) {
+    return !k_bb_chain_small(d) && k_bb_chain_supported(d, B) && (d.q_heads * 128) % 512 == 0 && d.hidden % 512 == 0 && d.inter % 512 == 0;
+}
 
 // one shape's launches: the 64-row stage set (33-64 rows) or the 16-row one (1-32 rows); the debug library's A/B arms exist for the 1.7B triple
-template <int KO, int KH, int KI>
+// W8: the stage sets on fp8 weights (BbArgs: the W8 pointers and scales in place of the bf16 matrices)
+template <int KO, int KH, int KI, bool W8 = false>
 static int bb_launch_shape(const BbArgs& a, int B, hipStream_t stream) {
+#define BB_B32(MT_, HEAD_) bb_chain_b32_kernel<KO, KH, KI, MT_, HEAD_, W8>
+#define BB_B64(HEAD_) bb_chain_kernel<KO, KH, KI, 2, 4, 4, false, true, false, true, 0, HEAD_, false, false, W8>
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute((const void*)bb_chain_b32_kernel<KO, KH, KI, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)bb_chain_b32_kernel<KO, KH, KI, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)bb_chain_b32_kernel<KO, KH, KI, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)bb_chain_b32_kernel<KO, KH, KI, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)bb_chain_kernel<KO, KH, KI, 2, 4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)bb_chain_kernel<KO, KH, KI, 2, 4, 4, false, true, false, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)BB_B32(1, false), hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)BB_B32(2, false), hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)BB_B32(1, true), hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)BB_B32(2, true), hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)BB_B64(false), hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)BB_B64(true), hipFuncAttributeMaxDynamicSharedMemorySize, BB_LDS_BYTES);
         attr = true;
     }
     const bool head = a.lm_head != nullptr;
     if (B <= 32) {
         if (B <= 16) {
-            if (head) hipLaunchKernelGGL((bb_chain_b32_kernel<KO, KH, KI, 1, true>), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
-            else hipLaunchKernelGGL((bb_chain_b32_kernel<KO, KH, KI, 1>), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
+            if (head) hipLaunchKernelGGL((BB_B32(1, true)), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
+            else hipLaunchKernelGGL((BB_B32(1, false)), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
         } else {
-            if (head) hipLaunchKernelGGL((bb_chain_b32_kernel<KO, KH, KI, 2, true>), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
-            else hipLaunchKernelGGL((bb_chain_b32_kernel<KO, KH, KI, 2>), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
+            if (head) hipLaunchKernelGGL((BB_B32(2, true)), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
+            else hipLaunchKernelGGL((BB_B32(2, false)), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
         }
         OMNI_CHECK_LAUNCH("bb_chain_b32");
         return OMNI_OK;
     }
-    if (head) hipLaunchKernelGGL((bb_chain_kernel<KO, KH, KI, 2, 4, 4, false, true, false, true, 0, true>), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL((bb_chain_kernel<KO, KH, KI, 2, 4, 4, false>), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
+    if (head) hipLaunchKernelGGL((BB_B64(true)), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
+    else hipLaunchKernelGGL((BB_B64(false)), dim3(OMNI_CHAIN_WGS), dim3(CH_THREADS), BB_LDS_BYTES, stream, a);
     OMNI_CHECK_LAUNCH("bb_chain");
     return OMNI_OK;
+#undef BB_B32
+#undef BB_B64
+}
+// (a listed triple with an odd width has no W8 instantiation: k_bb_chain_w8_supported keeps it on the launch path)
+template <int KO, int KH, int KI>
+static int bb_launch_w8(const BbArgs& a, int B, hipStream_t stream) {
+    if constexpr (KO % 2 == 0 && KH % 2 == 0 && KI % 2 == 0) return bb_launch_shape<KO, KH, KI, true>(a, B, stream);
+    omni_set_error("bb_chain: the W8 stage sets need reduction widths %% 512 == 0");
+    return OMNI_EINVAL;
 }
 
 // the all-reduce / half-grid instantiations of one triple (64-row stage set)
@@ -371,11 +403,19 @@ bool k_bb_chain_head_supported(const omni_talker_desc& d) {      // the lm_head 
 
 int k_bb_chain(const omni_talker_desc& d, const omni_layer_weights& w, const omni_layer_weights* next, const void* attn, void* resid, float* part,
                void* act, void* qkv, int B, float eps, uint32_t* flags, int32_t* err, void* stream, bool small, const omni_bb_head* head,
-               const omni_bb_ar* ar, bool half) {
+               const omni_bb_ar* ar, bool half, const omni_dense_w8_layer* w8, const omni_dense_w8_layer* w8_next) {
     BbArgs a{};
     a.wo = (const uint16_t*)w.wo; a.ln2 = (const uint16_t*)w.ln2; a.wgu = (const uint16_t*)w.wgu; a.wdown = (const uint16_t*)w.wdown;
     a.ln1_next = next ? (const uint16_t*)next->ln1 : nullptr;
     a.wqkv_next = next ? (const uint16_t*)next->wqkv : nullptr;
+    if (w8 != nullptr) {      // the W8 stage sets: this layer's fp8 bytes and row scales, the next layer's qkv
+        OMNI_CHECK_ARG(!small && ar == nullptr && !half && (next == nullptr || w8_next != nullptr) && k_bb_chain_w8_supported(d, B),
+                       "bb_chain: the W8 stage sets serve a single rank's full grid on a listed shape with reduction widths %% 512 == 0");
+        a.wo = (const uint16_t*)w8->wo; a.wgu = (const uint16_t*)w8->wgu; a.wdown = (const uint16_t*)w8->wdown;
+        a.so = w8->wo_scale; a.sgu = w8->wgu_scale; a.sdown = w8->wdown_scale;
+        a.wqkv_next = next ? (const uint16_t*)w8_next->wqkv : nullptr;
+        a.sqkv_next = next ? w8_next->wqkv_scale : nullptr;
+    }
     a.attn = (const uint16_t*)attn; a.resid = (uint16_t*)resid; a.part = part; a.act = (uint16_t*)act; a.qkv = (uint16_t*)qkv;
     a.H = d.hidden; a.I = d.inter; a.NQ = (d.q_heads + 2 * d.kv_heads) * 128;
     a.B = B; a.nap = g_bb_nap; a.eps = eps; a.flags = flags; a.err = err;
@@ -409,6 +449,13 @@ int k_bb_chain(const omni_talker_desc& d, const omni_layer_weights& w, const omn
             return bb_launch_ar<8, 8, 24, false>(a, true, (hipStream_t)stream);
         }
         omni_set_error("bb_chain: no all-reduce / half-grid stage set for (q width, hidden, intermediate) = (%d, %d, %d)", d.q_heads * 128, d.hidden, d.inter);
+        return OMNI_EINVAL;
+    }
+    if (w8 != nullptr) {         // (every listed triple whose widths are whole 512-wide groups; the A/B arms below are bf16 stage sets)
+#define X(KO_, KH_, KI_) if (ko == KO_ && kh == KH_ && ki == KI_) return bb_launch_w8<KO_, KH_, KI_>(a, B, (hipStream_t)stream);
+        BB_SHAPES(X)
+#undef X
+        omni_set_error("bb_chain: no W8 stage set for (q width, hidden, intermediate) = (%d, %d, %d)", d.q_heads * 128, d.hidden, d.inter);
         return OMNI_EINVAL;
     }
 #ifdef OMNI_DEBUG_HOOKS      // the A/B arms of rounds 3-5 (1.7B triple only)

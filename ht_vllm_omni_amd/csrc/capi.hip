@@ -124,6 +124,7 @@ struct omni_talker {
     bool head_fused = false;            // the last backbone launch of the step in progress computed logits + h[t + 1] (run_backbone fuse_head)
     bool tail_fused = false;            // the predictor's all-pass launch of the step in progress assembled the backbone's input and computed layer 0's qkv
     std::vector<omni_dense_w8_layer> w8;   // omni_talker_set_dense_w8: fp8 bytes + row scales of the backbone's four GEMMs per layer (empty: off)
+    bool w8_chain = false;              // omni_talker_set_dense_w8_chain: a W8 engine's backbone takes the persistent launches' W8 stage sets where they exist
 };
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -377,12 +378,24 @@ extern "C" int omni_talker_set_dense_w8(omni_talker* t, const omni_dense_w8_laye
 }
 // ONE predicate for "the backbone runs as persistent launches" -- read by mtp_phase (does the predictor's launch assemble the input and run
 // layer 0's qkv?) and by run_backbone (which then skips that qkv): the two must never disagree (a stale qkv otherwise)
-static bool bb_chain_runs(const omni_talker* t, int B, bool half) {
-    return t->w8.empty() && !(t->has_ar && t->bb_ar_off) && t->d.layers > 0 &&
-           k_bb_chain_supported(t->d, B, t->has_ar ? &t->ar_attn : nullptr, half);
-}
 // the W8 entry points serve the deferred-rstd form only: with omni_debug_gemm_defer(0) the norm-fused GEMMs keep the bf16 kernel
 static bool w8_norm_fused(const omni_talker* t) { return !t->w8.empty() && k_gemm_defer(); }
+// the chain of a W8 engine (omni_talker_set_dense_w8_chain): the W8 stage sets of bb_chain.hip -- same bits as the W8 launches
+static bool bb_chain_w8(const omni_talker* t, int B, bool half) {
+    return t->w8_chain && !t->w8.empty() && !t->has_ar && !half && w8_norm_fused(t) && k_bb_chain_w8_supported(t->d, B);
+}
+static bool bb_chain_runs(const omni_talker* t, int B, bool half) {
+    if (!t->w8.empty()) return t->d.layers > 0 && bb_chain_w8(t, B, half);
+    return !(t->has_ar && t->bb_ar_off) && t->d.layers > 0 && k_bb_chain_supported(t->d, B, t->has_ar ? &t->ar_attn : nullptr, half);
+}
+// A W8 engine's backbone as persistent launches (bb_chain.hip W8 stage sets) instead of launch per op: on != 0 takes them wherever
+// bb_chain_w8 holds, every other case and on == 0 keep omni_talker_set_dense_w8's launch-per-op step.  Per handle, independent of the order
+// of the two calls; survives omni_talker_set_chains (off: the W8 launches; on again: the W8 chain).  Call before capturing graphs.
+extern "C" int omni_talker_set_dense_w8_chain(omni_talker* t, int on) {
+    OMNI_CHECK_ARG(t, "omni_talker_set_dense_w8_chain: null engine");
+    t->w8_chain = on != 0;
+    return OMNI_OK;
+}
 // per-layer fp8 KV scales (host arrays [layers]) after a calibration pass: the device copy the captured decode steps read, and the
 // host copy the eager prefill launches pass as arguments
 extern "C" int omni_talker_set_kv_scales(omni_talker* t, const float* k_scale, const float* v_scale, void* stream) {
@@ -1028,7 +1041,8 @@ static int run_backbone(omni_talker* t, const omni_step_io* io, void* stream, in
                 const bool with_head = last && fuse_head && !t->chain_half && g_bb_head && k_bb_chain_head_supported(d);      // (the half grid has no head stage)
                 TRY(k_bb_chain(d, w, last ? nullptr : &t->layer[l + 1], t->attn, t->resid, t->part, t->act, t->qkv, B, d.eps,
                                t->chain_flags, reinterpret_cast<int32_t*>(t->chain_flags + 320), stream, plain && k_bb_chain_small(d), with_head ? &hd : nullptr,
-                               t->has_ar ? &bar : nullptr, t->chain_half));
+                               t->has_ar ? &bar : nullptr, t->chain_half, t->w8.empty() ? nullptr : &t->w8[l],
+                               t->w8.empty() || last ? nullptr : &t->w8[l + 1]));
                 if (with_head) t->head_fused = true;
             }
         }

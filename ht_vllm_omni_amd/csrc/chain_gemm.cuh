@@ -42,6 +42,12 @@
 //        loads stay in flight through the barrier, the flag and the next hand-off.  (Issued earlier -- behind the last
 //        activation load -- they sit in front of the stores in the wave's in-order queue and the flag waits for the whole
 //        slice: measured +0.2 ms per step.)
+//        4: fp8 e4m3fn bytes in the W8 fragment layout (include/omni_talker.h; gemm_w8.hip), whole slice ahead of the flags: the 1-KB block
+//        p * 8 + wave of a 16-row tile IS this wave's k-steps d = 2 p and 2 p + 1 (8 B per lane each), so one 16-B load per tile feeds two
+//        MFMA groups from 4 registers where bf16 holds 8 -- NT * NTW / 2 loads per wave plus one row scale per tile (lane (r, q) owns row r).
+//        Behind the flags each half is rebuilt as bf16(fp8 * scale) (deq_fp8x8) in front of its MFMAs, the pair's second half under the
+//        first half's MFMAs (gemm_w8_kernel::mma_pair).  Same k-step ownership, accumulation order, combine and epilogue: the bits of
+//        omni_gemm_xnorm_w8 / omni_gemm_resid_w8, hence of WSRC 0 on the dequantised matrix.  Whole 512-wide groups only (NTW even).
 struct ChainNoPrefetch { static constexpr int LOADS = 0; __device__ __forceinline__ void operator()() const {} };
 // ---- round 6: the tensor-parallel all-reduce INSIDE a residual stage (bb_chain.hip on a tensor-parallel rank; allreduce.hip is the same
 // exchange as a launch of its own).  The stage's workgroup owns one 16-column x (16 MT)-row tile of the row-parallel GEMM's output on EVERY
@@ -84,7 +90,8 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
                                            for the NEXT launch), written by the workgroup columns bx < 8 as gemm_skinny_kernel spreads them */,
                                            const uint8_t* mask = nullptr /* EPI_F32_BF16RND: logit n is `mask_fill` where mask[n] == 0 (the codec mask) */,
                                            float mask_fill = 0.f, const int32_t* nlive_ptr = nullptr /* normed_out: rows >= *nlive_ptr are not written */,
-                                           const ChainAr* ar = nullptr, uint32_t ar_epoch = 0 /* AR: the exchange's peers and its call number */) {
+                                           const ChainAr* ar = nullptr, uint32_t ar_epoch = 0 /* AR: the exchange's peers and its call number */,
+                                           const float* w_scale = nullptr /* WSRC 4: fp32 scale per row of W (W = the fp8 bytes) */) {
     const int sidx = ((code & 255) >> 4) * 5 + (code & 15) - 1;
     constexpr int G = (XG == 0 || XG > NTW) ? NTW : XG;
     constexpr bool NORM = PRO == 2 || PRO == 3, DEFER = PRO == 3;
@@ -95,7 +102,10 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
     // OMNI_EPI_SILU_MUL (round 5: the MoE layer's shared expert): W = [gate rows | up rows], n-tiles [0, NT/2) are gate tiles, [NT/2, NT)
     // the matching up tiles N rows further down (gemm_skinny_kernel's pairing); out = N activation columns
     constexpr bool SILU2 = EPI == OMNI_EPI_SILU_MUL;
-    constexpr bool WRING = WSRC == 1, WFIFO = WSRC == 2;
+    constexpr bool WRING = WSRC == 1, WFIFO = WSRC == 2, W8 = WSRC == 4;
+    static_assert(WSRC >= 0 && WSRC <= 4, "chain_gemm: weight source");
+    static_assert(!W8 || (NTW % 2 == 0 && G % 2 == 0 && PRO != 2 && !SILU2 && !AR),
+                  "chain_gemm W8: whole 16-step groups, both steps of a pair in the activation ring, plain or deferred-rstd prologue");
     static_assert(EPI == OMNI_EPI_BF16 || EPI == OMNI_EPI_RESID || EPI == OMNI_EPI_F32_BF16RND || GU8 || SILU2, "chain_gemm: epilogue");
     static_assert(!SILU2 || (NT % 2 == 0 && WSRC == 0 && NT * MT <= 6), "chain_gemm: plain SiLU-mul = gate / up tile pairs, whole slice ahead of the flags");
     // first 16-row tile of W behind n-tile j of this workgroup
@@ -119,8 +129,22 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
     // ---- before the flags: everything that does not depend on the previous stage.  (The polling wave's first poll returns
     // behind its own weight loads -- a wave's loads return in order -- but letting wave 0 fetch its share of the slice behind
     // the flags instead measured WORSE: the predictor 1.80 -> 2.11 ms; its weights then arrive later than the activations.)
-    constexpr int WS = (WFIFO || WSRC == 3) ? 1 : (WRING ? G : NTW);      // weight slots held at a time
+    constexpr int WS = (WFIFO || WSRC == 3) ? 1 : (WRING ? G : (W8 ? NTW / 2 : NTW));      // weight slots held at a time (W8: a slot = a pair of k-steps)
     u32x4 Wq[WS][NT], NWq[G];
+    float wsc[NT];                       // W8: the scale of this lane's row (lane & 15) of every n-tile
+#pragma unroll
+    for (int j = 0; j < NT; ++j) wsc[j] = 0.f;
+    if (W8) {
+        // a tile's K bytes x 16 rows = nsteps / 2 blocks of 1 KB; pair p of this wave = block p * 8 + wave
+        const coh_rsrc_t srs = coh_rsrc(w_scale);
+#pragma unroll
+        for (int p = 0; p < NTW / 2; ++p)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                Wq[p % WS][j] = __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, (uint32_t)((wtile(j) * (nsteps / 2) + p * CH_WAVES + wave) * 1024), WAUX);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) wsc[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srs, (lane & 15) * 4, (uint32_t)(wtile(j) * 64), 0));
+    }
 #pragma unroll
     for (int d = 0; d < NTW; ++d) {
         const int ks = wave + d * CH_WAVES;
@@ -201,6 +225,7 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
     for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int i = 0; i < MT; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    u32x4 Wodd[NT];                      // W8: the pair's second k-step, converted under the MFMAs of the first
 #pragma unroll
     for (int d = 0; d < NTW; ++d) {
         u32x4 Xn[MT], Wn[NT];
@@ -216,6 +241,10 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
         } else if (WSRC == 3) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) Wn[j] = Wpre[d][j];
+        } else if (W8) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                Wn[j] = d % 2 == 0 ? deq_fp8x8((u32x2){Wq[(d / 2) % WS][j][0], Wq[(d / 2) % WS][j][1]}, wsc[j]) : Wodd[j];
         } else {
 #pragma unroll
             for (int j = 0; j < NT; ++j) Wn[j] = Wq[WRING ? d % G : d][j];
@@ -235,6 +264,10 @@ __device__ __forceinline__ void chain_gemm(const uint16_t* __restrict__ W, const
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int i = 0; i < MT; ++i) acc[j][i] = mfma16(Wn[j], Xn[i], acc[j][i]);
+        if (W8 && d % 2 == 0) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) Wodd[j] = deq_fp8x8((u32x2){Wq[(d / 2) % WS][j][2], Wq[(d / 2) % WS][j][3]}, wsc[j]);
+        }
         if (WFIFO) eng_release(g, wave, g.piece_base + (unsigned)(d + 1) * (8 * NT));      // the MFMAs above hold the fragments: the pieces are free
     }
 

@@ -109,7 +109,10 @@ struct omni_bb_ar { const omni_ar_peers* attn; const omni_ar_peers* mlp; };     
 bool k_bb_chain_head_supported(const omni_talker_desc& d);
 int k_bb_chain(const omni_talker_desc& d, const omni_layer_weights& w, const omni_layer_weights* next, const void* attn, void* resid, float* part,
                void* act, void* qkv, int B, float eps, uint32_t* flags, int32_t* err, void* stream, bool small = false,
-               const omni_bb_head* head = nullptr, const omni_bb_ar* ar = nullptr, bool half = false);
+               const omni_bb_head* head = nullptr, const omni_bb_ar* ar = nullptr, bool half = false,
+               const omni_dense_w8_layer* w8 = nullptr /* the W8 stage sets: this layer's fp8 weights ... */,
+               const omni_dense_w8_layer* w8_next = nullptr /* ... and the next layer's (its qkv stage) */);
+bool k_bb_chain_w8_supported(const omni_talker_desc& d, int B);      // single rank, full grid, BB_SHAPES triple, every reduction width % 512 == 0
 // the sparse-MoE layer between its attention launch and its expert GEMMs (o_proj -> router | shared gate_up -> shared down + routing) as
 // one persistent launch (moe_chain.hip); supported = the Omni talker's shape on a single rank, <= 64 rows
 bool k_moe_chain_supported(const omni_talker_desc& d, int B, bool has_ar);

@@ -191,7 +191,12 @@ class TalkerEngine:
         # dense backbone decode on fp8 weights (csrc/gemm_w8.hip): the four backbone GEMMs of the decode step stream one byte per weight
         # and rebuild W_eff = bf16(fp8 * row scale) in registers; the bf16 W_eff copies stay for the prefill and the fall-backs, so
         # this buys decode bandwidth, not capacity (weight memory of the backbone grows by half)
+        # dense_fp8="chain": the same engine with the backbone's persistent launches on the fp8 bytes (csrc/bb_chain.hip W8 stage sets) where the
+        # shape has them -- same bits; True keeps the backbone launch per op
+        if isinstance(dense_fp8, str) and dense_fp8 != "chain":
+            raise ValueError(f"dense_fp8={dense_fp8!r}: True, False or 'chain'")
         self.dense_fp8 = bool(dense_fp8)
+        self.dense_fp8_chain = dense_fp8 == "chain"
         # prefill_gemm="fp8": the prefill's four GEMMs on those same bytes with per-token fp8 activations (csrc/gemm_prefill_f8.hip)
         # ... and on an MoE model with moe_fp8=True: the routed experts' two grouped GEMMs on the decode step's fp8 expert bytes (the MOE
         # instantiations of that file; ops.moe_prefill_experts), attention projections / router / shared expert on the bf16 tile GEMM
@@ -545,6 +550,7 @@ class TalkerEngine:
         """Hand the fp8 backbone weights to a native engine (after EVERY omni_talker_create: the setting lives in the handle)."""
         if self.dense_fp8:
             L.check(self.lib.omni_talker_set_dense_w8(handle, self._w8_layers), "omni_talker_set_dense_w8")
+            L.check(self.lib.omni_talker_set_dense_w8_chain(handle, int(self.dense_fp8_chain)), "omni_talker_set_dense_w8_chain")
 
     def kv_cache_bytes(self) -> int:
         return sum(c.numel() * c.element_size() for c in self.kv_caches) + sum(s.numel() * 4 for s in (self.kv_scales or []))

@@ -586,6 +586,14 @@ typedef struct omni_dense_w8_layer {
     const float *wqkv_scale, *wo_scale, *wgu_scale, *wdown_scale;
 } omni_dense_w8_layer;
 int omni_talker_set_dense_w8(omni_talker* t, const omni_dense_w8_layer* layers);
+/* The backbone's persistent launches ON those fp8 weights (additive to ABI v5; csrc/bb_chain.hip W8 stage sets).  on != 0: an engine with
+ * omni_talker_set_dense_w8 weights runs o_proj -> gate_up -> down_proj -> next qkv as one launch per layer whose stages read the same fp8
+ * bytes in place (omni_talker_chains_ran bit 1 set) -- same bits as its launch-per-op step -- where the shape has a stage set (the listed
+ * 1.7B-class triples), every reduction width (q_heads * head_dim, hidden, intermediate) is a multiple of 512, and the engine is a single rank
+ * on the full grid; everywhere else, and with on == 0 (the default), the step stays launch per op.  The lm_head stage, the code predictor
+ * and the prefill keep their bf16 weights.  The flag is per engine and independent of omni_talker_set_chains: chains off -> the W8 launches,
+ * on again -> the W8 chain.  Call before capturing graphs.                                                                  */
+int omni_talker_set_dense_w8_chain(omni_talker* t, int on);
 /* ABI v4.  Per-layer fp8 KV scales (host arrays [layers], all > 0) -- the result of a `calculate_kv_scales` pass: the reference
  * runs its first forward eager so that vLLM's attention layers can set k_scale = max|k| / 200, v_scale = max|v| / 100 from that
  * pass (V/worker/gpu_ar_model_runner.py:122,269-275).  The decode step's attention launches read the scales

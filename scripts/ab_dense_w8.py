@@ -1,5 +1,6 @@
 """Whole decode step, W3 (tts-1.7b, B = 64, fp8 KV, one hipGraph per step): the product default (bf16, persistent chains), bf16 with the
-backbone launch per op (omni_debug_bb_chain(0); the predictor keeps its chain, as under dense_fp8) and dense_fp8 -- three graphs in one
+backbone launch per op (omni_debug_bb_chain(0); the predictor keeps its chain, as under dense_fp8), dense_fp8 (W8 launch per op) and
+dense_fp8="chain" (the W8 stage sets of bb_chain.hip) -- four graphs in one
 process, timed round-robin over the same context window (mean context --ctx at its middle).  Report only: the default does not change.  usage: python scripts/ab_dense_w8.py [--steps 48] [--rounds 5]"""
 import argparse, ctypes as C, os, sys, types
 os.environ["OMNI_TALKER_DEBUG"] = "1"
@@ -21,13 +22,15 @@ torch.cuda.set_device(0)
 d = get_dims("tts-1.7b")
 w = make_weights(d, seed=1234, std=0.02, device="cuda")
 kw = dict(kv_dtype="fp8", num_blocks=args.num_blocks, block_size=16, max_batch=B, allow_eos=False)
-engines = {"bf16": TalkerEngine(d, dense_fp8_weights(d, w), **kw), "dense_fp8": TalkerEngine(d, w, dense_fp8=True, **kw)}
+engines = {"bf16": TalkerEngine(d, dense_fp8_weights(d, w), **kw), "dense_fp8": TalkerEngine(d, w, dense_fp8=True, **kw),
+           "dense_fp8 chain": TalkerEngine(d, w, dense_fp8="chain", **kw)}
 del w
 lib = engines["bf16"].lib
 lib.omni_debug_bb_chain.argtypes = [C.c_int]; lib.omni_debug_bb_chain.restype = None
 graphs = {}
-for name, eng, bb in (("bf16 chains (default)", engines["bf16"], 1), ("bf16 launch per op", engines["bf16"], 0), ("dense_fp8", engines["dense_fp8"], 1)):
-    if name.startswith("bf16 chains") or name == "dense_fp8":
+for name, eng, bb in (("bf16 chains (default)", engines["bf16"], 1), ("bf16 launch per op", engines["bf16"], 0), ("dense_fp8", engines["dense_fp8"], 1),
+                      ("dense_fp8 chain", engines["dense_fp8 chain"], 1)):
+    if not hasattr(eng, "start"):
         eng.set_sampling(greedy=0, temperature=0.9, top_k=50, rep_penalty=1.05, seed=42, cp_greedy=0, cp_temperature=0.9, cp_top_k=50)
         bench.setup_requests(d, eng, args)
         for _ in range(a.ctx - int(eng.seq_lens[:B].float().mean().item()) - a.steps // 2):
