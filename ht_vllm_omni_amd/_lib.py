@@ -89,6 +89,23 @@ class ResUnit(C.Structure):
                 ("w2", vp), ("b2", vp), ("next_alpha", vp), ("next_inv_beta", vp), ("T", i32), ("C", i32), ("dilation", i32)]
 
 
+SPK_MAX_LAYERS = 8
+SPK_ACT_NONE, SPK_ACT_RELU, SPK_ACT_TANH, SPK_ACT_RELU_TANH = 0, 1, 2, 3
+
+
+class SpkBlock(C.Structure):
+    """omni_spk_block: one SE-Res2Net block of the speaker encoder (weights as include/omni_talker.h lays them out)."""
+    _fields_ = [(n, vp) for n in ("tdnn1_w", "tdnn1_b", "res_w", "res_b", "tdnn2_w", "tdnn2_b", "se1_w", "se1_b", "se2_w", "se2_b")]
+
+
+class SpkDesc(C.Structure):
+    """omni_spk_desc: shapes (Qwen3TTSSpeakerEncoderConfig) + device weights of the speaker encoder."""
+    _fields_ = [("mel_dim", i32), ("enc_dim", i32), ("layers", i32), ("scale", i32), ("se_channels", i32), ("att_channels", i32),
+                ("channels", i32 * SPK_MAX_LAYERS), ("kernels", i32 * SPK_MAX_LAYERS), ("dilations", i32 * SPK_MAX_LAYERS),
+                ("conv0_w", vp), ("conv0_b", vp), ("blocks", SpkBlock * (SPK_MAX_LAYERS - 2)), ("mfa_w", vp), ("mfa_b", vp),
+                ("att_wh", vp), ("att_wms", vp), ("att_b", vp), ("att_conv_w", vp), ("att_conv_b", vp), ("fc_w", vp), ("fc_b", vp)]
+
+
 class TalkerDesc(C.Structure):
     _fields_ = [
         ("hidden", i32), ("layers", i32), ("q_heads", i32), ("kv_heads", i32), ("head_dim", i32), ("inter", i32),
@@ -162,6 +179,11 @@ SIGNATURES = {
     "omni_gemm_w8": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "omni_gemm_resid_w8": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
     "omni_gemm_xnorm_w8": (i32, [vp, vp, i32, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "omni_spk_scratch_bytes": (i64, [C.POINTER(SpkDesc), i32]),
+    "omni_spk_encode": (i32, [C.POINTER(SpkDesc), vp, i32, vp, vp, vp]),
+    "omni_spk_conv": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "omni_spk_res2net": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "omni_spk_asp": (i32, [C.POINTER(SpkDesc), vp, i32, vp, vp, vp]),
     "omni_talker_set_dense_w8": (i32, [vp, C.POINTER(DenseW8Layer)]),
     "omni_talker_set_dense_w8_chain": (i32, [vp, i32]),
     "omni_attn_decode_fused": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,

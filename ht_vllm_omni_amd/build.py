@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libomni_talker.so")
 LIB_DEBUG = os.path.join(HERE, "libomni_talker_debug.so")
 SOURCES = ["capi.hip", "gemm.hip", "gemm_w8.hip", "gemm_prefill.hip", "gemm_prefill_f8.hip", "norm.hip", "rope_kv.hip", "paged_attn.hip", "prefill_attn.hip", "moe.hip",
-           "moe_prefill.hip", "sampler.hip", "cp_chain.hip", "bb_chain.hip", "moe_chain.hip", "allreduce.hip", "codec.hip", "conv_unit.hip"]
+           "moe_prefill.hip", "sampler.hip", "cp_chain.hip", "bb_chain.hip", "moe_chain.hip", "allreduce.hip", "codec.hip", "conv_unit.hip", "spk_encoder.hip"]
 # debug library only: the probes, and the losing A/B arms of the backbone chain (rounds 3 and 4; no product knob reaches them)
 DEBUG_ONLY = ["debug.hip", "bb_engine.hip", "bb_all.hip"]
 # per-file extra flags

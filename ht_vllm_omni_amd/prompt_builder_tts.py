@@ -11,7 +11,9 @@ the in-context codec sum is accumulated in fp32 in group order on the device; as
 does not depend on its batch mates, so the outputs are the reference's.
 
 Out of scope, and taken as inputs: the text tokenizer (a checkpoint asset: pass token ids, or a `tokenize` callable) and
-the audio front end of voice cloning (speaker encoder / reference-audio codec: pass `ref_spk_embedding` / `ref_code`).
+the reference-audio codec of in-context voice cloning (pass `ref_code`).  The speaker embedding of a Base request is either passed
+(`ref_spk_embedding`) or computed from `ref_audio` by the builder's `speaker_encoder` (speaker.SpeakerEncoder, 24 kHz audio;
+qwen3_tts_talker.py:1376-1386).
 """
 from __future__ import annotations
 
@@ -79,7 +81,8 @@ def instruct_text(instruct: str) -> str:
 
 
 class TTSTalkerPromptBuilder:
-    def __init__(self, weights: dict, ids: TTSPromptIds, device: str | torch.device = "cuda", tokenize: Callable[[str], list[int]] | None = None):
+    def __init__(self, weights: dict, ids: TTSPromptIds, device: str | torch.device = "cuda", tokenize: Callable[[str], list[int]] | None = None,
+                 speaker_encoder=None):
         """weights: {"text_embedding" [Vt, Ht], "text_projection" {fc1_w, fc1_b, fc2_w, fc2_b}, "codec_embed" [V, H] (the talker's
         codec embedding = engine `embed`), "cp_embed" [Q-1, Vc, H]} -- checkpoint.load_talker_checkpoint's extras / weights."""
         self.dev = torch.device(device)
@@ -88,8 +91,22 @@ class TTSTalkerPromptBuilder:
         self.w_proj = {k: up(v) for k, v in weights["text_projection"].items()}
         self.codec_embed = up(weights["codec_embed"])
         self.cp_embed = up(weights["cp_embed"])
-        self.ids, self.tokenize = ids, tokenize
+        self.ids, self.tokenize, self.speaker_encoder = ids, tokenize, speaker_encoder
         self.hidden = int(self.codec_embed.shape[1])
+
+    @classmethod
+    def from_checkpoint(cls, extras: dict, codec_embed: torch.Tensor, cp_embed: torch.Tensor, ids: TTSPromptIds, device="cuda", tokenize=None,
+                        speaker_encoder_config: Any = None) -> "TTSTalkerPromptBuilder":
+        """The builder over checkpoint.load_talker_checkpoint's extras: the text tables, and -- where the checkpoint ships
+        `speaker_encoder.*` tensors (the Base variants) -- the speaker encoder, so that a Base request may carry `ref_audio`."""
+        tp = "text_projection.linear_fc"
+        w = {"text_embedding": extras["text_embedding.weight"], "codec_embed": codec_embed, "cp_embed": cp_embed,
+             "text_projection": {"fc1_w": extras[tp + "1.weight"], "fc1_b": extras[tp + "1.bias"], "fc2_w": extras[tp + "2.weight"], "fc2_b": extras[tp + "2.bias"]}}
+        enc = None
+        if any(k.startswith("speaker_encoder.") for k in extras):
+            from .speaker import SpeakerEncoder
+            enc = SpeakerEncoder.from_state_dict(extras, speaker_encoder_config, device)
+        return cls(w, ids, device, tokenize, speaker_encoder=enc)
 
     # ---- request-level resolution (talker.py:1254-1269, 1458-1466, 1226-1230)
     def resolve(self, task_type: str, info: dict) -> dict:
@@ -142,6 +159,9 @@ class TTSTalkerPromptBuilder:
         ref_code = _first(vcp.get("ref_code"))
         spk = vcp.get("ref_spk_embedding")
         if task == "Base":
+            ref_audio = info.get("ref_audio")
+            if spk is None and self.speaker_encoder is not None and ref_audio is not None:
+                spk = self.speaker_encoder.embed_audio(ref_audio)      # 24 kHz only: any other rate is a ValueError (resampling is upstream)
             if spk is None:
                 raise ValueError("Base requires a speaker embedding (voice_clone_prompt.ref_spk_embedding): the speaker encoder runs upstream")
             if icl and ref_code is None:

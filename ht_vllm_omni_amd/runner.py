@@ -317,6 +317,7 @@ class MI355XARModelRunner:
             elif pe is None and getattr(self.prompt_builder, "from_info", None) is not None and (info.get("text") or info.get("input_ids") is not None):
                 # Qwen3-TTS request (text / task_type / speaker / voice_clone_prompt): _build_prompt_embeds on the device
                 # (prompt_builder_tts.TTSTalkerPromptBuilder = qwen3_tts_talker.py:1211-1567)
+                # a Base request's `ref_audio` becomes its speaker embedding there when the builder holds the checkpoint's speaker encoder
                 tp = self.prompt_builder.from_info(info)
                 pe, tail, pad = tp.embeds, tp.trailing_text_hidden, tp.tts_pad
                 if tp.ref_code is not None:

@@ -263,6 +263,7 @@ class MI355XARWorker:
             from .tp_comm import check_backbone_chain
             self.tp_backbone_chain = check_backbone_chain(self.engine, log=logger.info)
         self._embed_table = self._weights["embed"]
+        self._cp_embed_table = self._weights.get("cp.embed")
         self._weights = None
 
     def initialize_from_config(self, kv_cache_config: Any = None) -> None:
@@ -296,6 +297,14 @@ class MI355XARWorker:
             pw = dict(pb_cfg["weights"])
             pw.setdefault("codec_embed", embed_table)        # talker.embed_input_ids = the talker's own codec table
             builder = OmniTalkerPromptBuilder(pw, ids, self.device)
+        # Qwen3-TTS talker: config.tts_prompt_builder = {"ids": TTSPromptIds, "tokenize": callable | None, "speaker_encoder_config": ...}; the
+        # text tables and the speaker encoder come from the checkpoint's extras (speaker_encoder.* -> speaker.SpeakerEncoder: a Base
+        # request may then carry `ref_audio` instead of `ref_spk_embedding`)
+        tts_cfg, extras = getattr(cfg, "tts_prompt_builder", None), getattr(self, "checkpoint_extras", None)
+        if builder is None and tts_cfg and extras:
+            from .prompt_builder_tts import TTSTalkerPromptBuilder
+            builder = TTSTalkerPromptBuilder.from_checkpoint(extras, embed_table, self._cp_embed_table, tts_cfg["ids"], self.device,
+                                                             tokenize=tts_cfg.get("tokenize"), speaker_encoder_config=tts_cfg.get("speaker_encoder_config"))
         self.model_runner = MI355XARModelRunner(self.engine, kv_transfer=OmniKVTransferManager(conn),
                                                 use_graphs=not getattr(cfg, "enforce_eager", False), prompt_builder=builder,
                                                 async_scheduling=bool(getattr(cfg, "async_scheduling", False)))

@@ -457,6 +457,60 @@ int omni_ar_open(const void* ipc_handle64, void** ptr);
 int omni_ar_close(void* ptr);
 int omni_ar_free(void* ptr);
 
+/* ------------------------------------------------------------------ speaker encoder (additive to ABI v5; csrc/spk_encoder.hip)
+ *
+ * The ECAPA-TDNN speaker encoder of the Qwen3-TTS Base checkpoints (Qwen3TTSSpeakerEncoder, V/model_executor/models/qwen3_tts/
+ * qwen3_tts_talker.py:57-239, run by _extract_speaker_embedding :1069-1105 for a request that carries `ref_audio`): log-mel bf16
+ * [T, mel_dim] time-major -> embedding bf16 [enc_dim].  Shapes = Qwen3TTSSpeakerEncoderConfig (configuration_qwen3_tts.py:21-69):
+ * channels / kernels / dilations [layers]: layer 0 the first TDNN, layers 1 .. layers - 2 the SE-Res2Net blocks, the last the aggregation
+ * layer.  Supported: every width (mel_dim, channels, channels / scale, se_channels, att_channels) a multiple of 16; channels[0 .. layers - 2]
+ * equal (= C), channels[layers - 1] = (layers - 2) C; odd kernel sizes with dilation * (kernel - 1) / 2 <= 4, last kernel 1; C / scale <= 64,
+ * (scale - 1) * dilation * (kernel - 1) / 2 <= 32 and (C / scale)^2 * kernel <= 16384 in the Res2Net blocks; T > 4.  Everything else is
+ * OMNI_EINVAL.  bf16 operands, fp32 accumulation, fp32 between two stored tensors, one rounding per stored tensor; fixed reduction orders
+ * (bit-identical runs); no host read, no allocation: capture-safe.
+ *
+ * Weights (device).  A conv weight torch [N, C_in, k] is stored as the bf16 matrix [N, K], K index = tap * C_in + channel, in MFMA tile
+ * order with KW = 32 when C_in % 32 == 0, else 16, and E = KW / 4: tile (n / 16, K / KW) = KW * 16 contiguous elements, element (row, kk) of
+ * a tile at ((kk / E) * 16 + row) * E + kk % E (KW = 32: OMNI_LAYOUT_W_FRAG).  res_w: the scale - 1 matrices [w, k w] of a block one after
+ * the other, res_b fp32 [(scale - 1) w].  Mat-vec weights (se1_w [se, C], se2_w [C, se], att_wms [att, 2 C3] = columns C3 .. 3 C3 of the
+ * attention TDNN, fc_w [enc_dim, 2 C3]) are bf16 row-major; att_wh = its columns 0 .. C3 as a conv matrix.  Every bias is fp32. */
+#define OMNI_SPK_MAX_LAYERS 8
+#define OMNI_SPK_ACT_NONE 0
+#define OMNI_SPK_ACT_RELU 1
+#define OMNI_SPK_ACT_TANH 2
+#define OMNI_SPK_ACT_RELU_TANH 3   /* tanh(relu(y)): the attention TDNN of the pooling layer */
+typedef struct omni_spk_block {
+    const void* tdnn1_w; const float* tdnn1_b;
+    const void* res_w; const float* res_b;
+    const void* tdnn2_w; const float* tdnn2_b;
+    const void* se1_w; const float* se1_b;
+    const void* se2_w; const float* se2_b;
+} omni_spk_block;
+typedef struct omni_spk_desc {
+    int mel_dim, enc_dim, layers, scale, se_channels, att_channels;
+    int channels[OMNI_SPK_MAX_LAYERS], kernels[OMNI_SPK_MAX_LAYERS], dilations[OMNI_SPK_MAX_LAYERS];
+    const void* conv0_w; const float* conv0_b;
+    omni_spk_block blocks[OMNI_SPK_MAX_LAYERS - 2];
+    const void* mfa_w; const float* mfa_b;
+    const void* att_wh; const void* att_wms; const float* att_b;
+    const void* att_conv_w; const float* att_conv_b;
+    const void* fc_w; const float* fc_b;
+} omni_spk_desc;
+/* bytes of scratch omni_spk_encode / omni_spk_asp need for T frames (negative: error) */
+int64_t omni_spk_scratch_bytes(const omni_spk_desc* desc, int T);
+/* mel bf16 [T, mel_dim] -> out bf16 [enc_dim] */
+int omni_spk_encode(const omni_spk_desc* desc, const void* mel, int T, void* out, void* scratch, void* stream);
+/* One reflect-"same"-padded dilated conv1d (TimeDelayNetBlock :60-74): out bf16 [T, ldo] = act(conv(x bf16 [T, ldx]) + bias), N outputs. */
+int omni_spk_conv(const void* x, int ldx, const void* w, const float* bias, void* out, int ldo, int T, int C_in, int N, int kernel,
+                  int dilation, int act, void* stream);
+/* One Res2Net block (Res2NetBlock :77-100) in one launch: x bf16 [T, ldx] of C = scale * w channels -> out bf16 [T, ldo]: chunk 0 copied,
+ * chunk i = relu(conv_i(x chunk i + chunk i - 1 of out)), the sum rounded to bf16 once; out must not alias x. */
+int omni_spk_res2net(const void* x, int ldx, const void* w, const float* bias, void* out, int ldo, int T, int C, int scale, int kernel,
+                     int dilation, void* stream);
+/* Attentive statistics pooling (AttentiveStatisticsPooling :138-180) with desc's weights: h bf16 [T, C3] contiguous -> stats fp32 [2 C3] =
+ * [weighted mean | weighted std]; scratch as omni_spk_scratch_bytes(desc, T). */
+int omni_spk_asp(const omni_spk_desc* desc, const void* h, int T, float* stats, void* scratch, void* stream);
+
 /* ------------------------------------------------------------------ talker engine */
 
 typedef struct omni_layer_weights {
