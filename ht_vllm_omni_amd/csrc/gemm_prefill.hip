@@ -24,8 +24,12 @@
 // stand-alone activation pass runs over the 24 kHz-rate tensors.
 // Workgroups are dealt to the 8 XCDs in contiguous chunks of the (n block, m block) order, m fastest: the workgroups that
 // share an L2 share a W panel.
+// This file holds what is bf16's own: the staging, the ring and its counted waits, the two kernels' MFMA schedules, and the entry point's
+// argument checks.  Shared with the fp8 sibling (gemm_prefill_f8.hip) and written once in tile_epi.cuh: geometry, tile order, launcher,
+// the MoE gate / up pairing and finishes, the epilogue.  Which geometry and form a launch takes: tile_choice_bf16, gemm_tile_policy.h.
 #include "common.cuh"
 #include "gemm_frag.cuh"
+#include "gemm_tile_policy.h"
 #include "kernels.h"
 #include "tile_epi.cuh"
 
@@ -33,33 +37,13 @@ __device__ __forceinline__ f32x4 tg_mfma(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-// Geometry of one instantiation: 8 waves (two per SIMD: while one issues its LDS-DMA pieces -- 60 - 180 cycles each -- or waits
-// for fragments, the other feeds the matrix pipe) as WAVES_N x (8 / WAVES_N); a wave owns WN n-tiles x WM m-tiles of 16 x 16
-// (acc = WN * WM * 4 of its 256 registers); BN = WAVES_N * WN * 16, BM = (8 / WAVES_N) * WM * 16.
-template <int WAVES_N, int WN, int WM>
-struct TileGeom {
-    static constexpr int WAVES_M = TG_WAVES / WAVES_N;
-    static constexpr int NTILES = WAVES_N * WN, MTILES = WAVES_M * WM;
-    static constexpr int BN = NTILES * 16, BM = MTILES * 16;
-    static constexpr int SLICE = (NTILES + MTILES) * 1024;                   // one 32-deep slice of both operands
-    static constexpr int NLW = (NTILES + TG_WAVES - 1) / TG_WAVES, NLX = (MTILES + TG_WAVES - 1) / TG_WAVES;   // LDS-DMA per wave and slice
-    static constexpr bool W_RAGGED = NTILES % TG_WAVES != 0;                 // some waves issue a dummy W load (uniform counts)
-    static constexpr bool X_RAGGED = MTILES % TG_WAVES != 0;                 // likewise for x (the 64-row tile of the small-M geometry)
-    static constexpr bool RAGGED = W_RAGGED || X_RAGGED;
-    static constexpr int NBUF = (TG_LDS_MAX - (RAGGED ? TG_WAVES * 1024 : 0)) / SLICE >= 4 ? 4 : 3;
-    static constexpr int EPI_BYTES = TG_WAVES * 16 * (WN * 64 + 16);           // fp32 image of one m-tile x the wave's columns
-    static constexpr int RING_BYTES = NBUF * SLICE + (RAGGED ? TG_WAVES * 1024 : 0);
-    static constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
-    static_assert(WN % 2 == 0 && LDS_BYTES <= TG_LDS_MAX, "geometry");
-};
-
+// Geometry TileGeom<WAVES_N, WN, WM> (tile_epi.cuh): one slice = a 32-deep 1-KB chunk of every tile of both operands.
 // MOE != 0: the same staging, ring and slice order over the MoE prefill's compact batch (one m block = BM rows of ONE expert):
-//   MOE_GU_FUSED  x rows gathered through row_token; W = the decode step's [gate rows | up rows] matrix (a.N = 2 I rows): n block nb covers
-//                 columns [nb BN/2, + BN/2) of gate AND of up, the first WN/2 n-tiles of a wave being gate and the second WN/2 the SAME columns
-//                 of up -- gate and up of an output element meet in one lane, SiLU(gate) * up runs in registers, out = act [rows, I];
+//   MOE_GU_FUSED  x rows gathered through row_token; W = the decode step's [gate rows | up rows] matrix (a.N = 2 I rows) in the gate / up
+//                 pairing of tile_src_ntile, SiLU(gate) * up in registers, out = act [rows, I];
 //   MOE_GU_PLAIN  x gathered, plain [rows, 2 I] output (widths the fused arrangement does not divide; omni_silu_mul follows);
 //   MOE_DOWN      x = act rows as they lie, out = bf16(bf16(acc) * row_weight[row]).
-// (the mode numbers: kernels.h)
+// (the mode numbers: kernels.h; the finishes: tile_moe_finish)
 template <int WAVES_N, int WN, int WM, bool GU8, int MOE = 0>
 __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_in) {
     using G = TileGeom<WAVES_N, WN, WM>;
@@ -107,15 +91,8 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
 #pragma unroll
     for (int i = 0; i < NLW; ++i) {
         const int f = wave + TG_WAVES * i;
-        int n16 = (n0 >> 4) + f;
-        bool in_n = n16 * 16 < a.N;
-        if constexpr (MOE == MOE_GU_FUSED) {                                  // tile f = n-tile j of wave column f / WN: gate (j < WN / 2) or up
-            constexpr int HN = WN / 2;
-            const int j = f % WN;
-            const int col16 = n_blk * (NTILES / 2) + (f / WN) * HN + j % HN;  // 16-column tile of the [rows, I] output
-            in_n = col16 * 32 < a.N;
-            n16 = (j >= HN ? a.N >> 5 : 0) + col16;
-        }
+        bool in_n;
+        const int n16 = tile_src_ntile<MOE, WN, NTILES>(f, n_blk, a.N, in_n);
         wbase[i] = (f < NTILES && in_n) ? (unsigned)((size_t)n16 * nsteps * 1024 + lane * 16) : TG_OOB;
     }
 #pragma unroll
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
     u32x4 xa[WM], xb[WM], w0[HW], w1[HW];
 #pragma unroll
     for (int s = 0; s < NBUF - 1; ++s) stage(s);
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(INFLIGHT * (NLW + NLX)) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(INFLIGHT * G::LOADS) : "memory");
 #pragma unroll
     for (int i = 0; i < WM; ++i) xa[i] = lds_x(0, i);
 #pragma unroll
@@ -189,7 +166,7 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
         _Pragma("unroll") for (int j = 0; j < HW; ++j)                                                       \
             _Pragma("unroll") for (int i = 0; i < WM; ++i) acc[j][i] = tg_mfma(w0[j], XCUR[i], acc[j][i]);   \
         __builtin_amdgcn_s_setprio(0);                                                                       \
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(INFLIGHT * (NLW + NLX)) : "memory"); \
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(INFLIGHT * G::LOADS) : "memory"); \
         _Pragma("unroll") for (int i = 0; i < WM; ++i) XNEXT[i] = lds_x((T) + 1, i);                         \
         _Pragma("unroll") for (int j = 0; j < HW; ++j) w0[j] = lds_w((T) + 1, j);                            \
         __builtin_amdgcn_s_setprio(1);                                                                       \
@@ -204,30 +181,9 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_kernel(const TileArgs a_
 #undef TG_SLICE
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is dead: its tail loads (zeros) landed
 
-    if constexpr (MOE == MOE_GU_FUSED) {
-        constexpr int HN = WN / 2;
-        f32x4 o[HN][WM];
-#pragma unroll
-        for (int j = 0; j < HN; ++j)
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[j][i][e] = silu_mul_bf16(acc[j][i][e], acc[HN + j][i][e]);
-        a.N >>= 1;                                                            // the output's width
-        tile_epilogue<HN, WM, false, true>(a, o, lds, wave, lane, m0 + wm * WM * 16, n_blk * (G::BN / 2) + wn * HN * 16);
-    } else if constexpr (MOE == MOE_DOWN) {
-        // the two rounding points of y = bf16(acc) followed by y * weight on bf16 tensors; the lane holds row (lane & 15) of m-tile i
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            const float wgt = bf2f(a.row_weight[m0 + (wm * WM + i) * 16 + c]);
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[j][i][e] = bfround(acc[j][i][e]) * wgt;
-        }
-        tile_epilogue<WN, WM, false, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
-    } else if constexpr (MOE == MOE_GU_PLAIN) {
-        tile_epilogue<WN, WM, false, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
+    if constexpr (MOE != 0) {
+        const int nw0 = MOE == MOE_GU_FUSED ? n_blk * (G::BN / 2) + wn * (WN / 2) * 16 : n0 + wn * WN * 16;
+        tile_moe_finish<MOE>(a, acc, lds, wave, lane, m0 + wm * WM * 16, nw0);
     } else {
         if (tile_plain(a)) tile_epilogue<WN, WM, GU8, true>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
         else tile_epilogue<WN, WM, GU8, false>(a, acc, lds, wave, lane, m0 + wm * WM * 16, n0 + wn * WN * 16);
@@ -435,40 +391,30 @@ static int launch_tile_pp(TileArgs a, hipStream_t st) {
 #else
     constexpr int LDS_BYTES = 128 * 1024 + TG_WAVES * 1024;
 #endif
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_pp_kernel<MW, GU8>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) { omni_set_error("omni_gemm_tile: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_tile_pp_kernel<MW, GU8>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), LDS_BYTES, st, a);
-    OMNI_CHECK_LAUNCH("omni_gemm_tile");
-    return OMNI_OK;
+    return tile_launch<gemm_tile_pp_kernel<MW, GU8>>(dim3(a.mblocks * a.nblocks), LDS_BYTES, a, st, "omni_gemm_tile");
 }
 
+template <int WAVES_N, int WN, int WM, bool GU8, int MOE = 0>
+static int launch_tile(const TileArgs& a, hipStream_t st, int groups = 1) {
+    return tile_launch_geom<gemm_tile_kernel<WAVES_N, WN, WM, GU8, MOE>, TileGeom<WAVES_N, WN, WM>>(
+        a, st, MOE ? "omni_moe_prefill_experts" : "omni_gemm_tile", groups);
+}
+
+// the instantiation a TileChoice (gemm_tile_policy.h) names
 template <bool GU8>
-static int launch_tile_pp_rows(int bm, const TileArgs& a, hipStream_t st) {
-    if (bm == 256) return launch_tile_pp<8, GU8>(a, st);
-    if (bm == 224) return launch_tile_pp<7, GU8>(a, st);
-    return launch_tile_pp<6, GU8>(a, st);
-}
-
-template <int WAVES_N, int WN, int WM, bool GU8>
-static int launch_tile(TileArgs a, hipStream_t st, int groups = 1) {
-    using G = TileGeom<WAVES_N, WN, WM>;
-    a.mblocks = (a.M + G::BM - 1) / G::BM;
-    a.nblocks = (a.N + G::BN - 1) / G::BN;
-    a.band = tile_band(a.mblocks, a.nblocks);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_kernel<WAVES_N, WN, WM, GU8>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) { omni_set_error("omni_gemm_tile: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
-        attr_set = true;
+static int launch_choice(const TileChoice& t, const TileArgs& a, hipStream_t st, int groups) {
+    if (t.mw) return t.mw == 8 ? launch_tile_pp<8, GU8>(a, st) : (t.mw == 7 ? launch_tile_pp<7, GU8>(a, st) : launch_tile_pp<6, GU8>(a, st));
+    switch (t.waves_n * 100 + t.wn * 10 + t.wm) {
+    case 422: return launch_tile<4, 2, 2, GU8>(a, st, groups);
+    case 284: return launch_tile<2, 8, 4, GU8>(a, st, groups);
+    case 447: return launch_tile<4, 4, 7, GU8>(a, st, groups);
+    case 446: return launch_tile<4, 4, 6, GU8>(a, st, groups);
+    case 184: return launch_tile<1, 8, 4, GU8>(a, st, groups);
+    case 264: if constexpr (!GU8) return launch_tile<2, 6, 4, false>(a, st, groups);        // (widths SiLU-mul never takes)
+    case 164: if constexpr (!GU8) return launch_tile<1, 6, 4, false>(a, st, groups);
     }
-    hipLaunchKernelGGL((gemm_tile_kernel<WAVES_N, WN, WM, GU8>), dim3(a.mblocks * a.nblocks, groups), dim3(TG_THREADS), G::LDS_BYTES, st, a);
-    OMNI_CHECK_LAUNCH("omni_gemm_tile");
-    return OMNI_OK;
+    omni_set_error("omni_gemm_tile: no kernel for tile <%d, %d, %d> mw=%d", t.waves_n, t.wn, t.wm, t.mw);
+    return OMNI_EINVAL;
 }
 
 extern "C" int omni_gemm_tile(const omni_tile_gemm* g, void* stream) {
@@ -505,70 +451,15 @@ extern "C" int omni_gemm_tile(const omni_tile_gemm* g, void* stream) {
     OMNI_CHECK_ARG(groups == 1 || (int64_t)groups * g->w_group_elems * 2 + (int64_t)g->N * g->K * 2 < ((int64_t)1 << 40), "omni_gemm_tile: W groups");
     a.gx_rows = groups > 1 ? g->x_group_rows : 0; a.gw_elems = groups > 1 ? g->w_group_elems : 0; a.gout_rows = groups > 1 ? g->out_group_rows : 0;
     a.group_rows = g->group_rows;
-    hipStream_t st = (hipStream_t)stream;
-    const int N = g->N;
-    // <waves along n, n tiles per wave, m tiles per wave>: 256 x 256 | 192 x 256 | 128 x 512 | 96 x 512 output tiles, and 128 x 64
-    // for problems whose big-tile grid would leave most of the 256 CUs idle (the Code2Wav transformer / ConvNeXt at a few hundred
-    // frames, streaming chunks): there the K loop's latency is the cost, not MFMA throughput
-    {
-        const int big_n = N % 256 == 0 ? 256 : (N % 192 == 0 ? 192 : (N % 128 == 0 ? 128 : (N % 96 == 0 ? 96 : (N > 128 ? 256 : 128))));
-        const int big_m = big_n >= 192 ? 256 : 512;
-        const long long big_tiles = (long long)((N + big_n - 1) / big_n) * ((g->M + big_m - 1) / big_m) * groups;
-        const bool small = g->tile_hint == 2 || (g->tile_hint == 0 && big_tiles < 96 && g->N >= 64);
-        if (small) return gu8 ? launch_tile<4, 2, 2, true>(a, st, groups) : launch_tile<4, 2, 2, false>(a, st, groups);
-    }
-    // 256-column tiles come in three heights.  One workgroup per CU (the ring takes most of the LDS), so a grid runs in rounds of
-    // 256 tiles and a round costs ~ the tile's rows: 6.4 k prompt tokens x 2048 columns are 208 tiles of 256 rows (one round, 48 CUs
-    // idle) or 232 tiles of 224 rows (one round, 12.5 % shorter).  Same accumulation order in every geometry: bit-identical results.
-    // A plain GEMM (no conv window, no groups) runs them in the two-group form (gemm_tile_pp_kernel: 5 - 8 % faster at every height).
-    if (N % 256 == 0) {
-        const bool pp_ok = groups == 1 && !g->group_rows && seg_len == g->K && g->row_off == 0;
-        OMNI_CHECK_ARG(g->tile_hint < 5 || pp_ok, "omni_gemm_tile: tile_hint=%d (two-group tile) takes a plain GEMM", g->tile_hint);
-        int bm = 256;
-        if (g->tile_hint == 3 || g->tile_hint == 6) bm = 224;
-        else if (g->tile_hint == 4 || g->tile_hint == 7) bm = 192;
-        else if (g->tile_hint == 0 && groups == 1) {
-            long long best = -1;
-            for (int cand : {256, 224, 192}) {
-                const long long tiles = (long long)((g->M + cand - 1) / cand) * (N / 256);
-                const long long cost = ((tiles + 255) / 256) * (cand + 16);
-                if (best < 0 || cost < best) { best = cost; bm = cand; }
-            }
-        }
-        if (g->tile_hint >= 5 || (g->tile_hint == 0 && pp_ok)) return gu8 ? launch_tile_pp_rows<true>(bm, a, st) : launch_tile_pp_rows<false>(bm, a, st);
-        if (bm == 224) return gu8 ? launch_tile<4, 4, 7, true>(a, st, groups) : launch_tile<4, 4, 7, false>(a, st, groups);
-        if (bm == 192) return gu8 ? launch_tile<4, 4, 6, true>(a, st, groups) : launch_tile<4, 4, 6, false>(a, st, groups);
-        return gu8 ? launch_tile<2, 8, 4, true>(a, st, groups) : launch_tile<2, 8, 4, false>(a, st, groups);
-    }
-    if (gu8) return launch_tile<1, 8, 4, true>(a, st, groups);
-    if (N % 192 == 0) return launch_tile<2, 6, 4, false>(a, st, groups);
-    if (N % 128 == 0) return launch_tile<1, 8, 4, false>(a, st, groups);
-    if (N % 96 == 0) return launch_tile<1, 6, 4, false>(a, st, groups);
-    return N > 128 ? launch_tile<2, 8, 4, false>(a, st, groups) : launch_tile<1, 8, 4, false>(a, st, groups);
+    const bool plain = groups == 1 && !g->group_rows && seg_len == g->K && g->row_off == 0;
+    OMNI_CHECK_ARG(g->tile_hint < 5 || plain, "omni_gemm_tile: tile_hint=%d (two-group tile) takes a plain GEMM", g->tile_hint);
+    const TileChoice t = tile_choice_bf16(g->M, g->N, groups, plain, gu8, g->tile_hint);
+    return gu8 ? launch_choice<true>(t, a, (hipStream_t)stream, groups) : launch_choice<false>(t, a, (hipStream_t)stream, groups);
 }
 
-// ---- the MoE prefill's expert GEMMs over the compact batch (entry points: moe_prefill.hip).  Two block heights with the K-slice order of
-// every other geometry (bit-identical expert outputs): 64 rows = <4, 2, 2> (128 columns; fused: 64 gate + 64 up), 256 rows = <2, 8, 4>
-// (256 columns; fused: 128 + 128).
-template <int WAVES_N, int WN, int WM, int MOE>
-static int launch_tile_moe(TileArgs a, hipStream_t st) {
-    using G = TileGeom<WAVES_N, WN, WM>;
-    a.mblocks = a.M / G::BM;
-    a.nblocks = MOE == MOE_GU_FUSED ? (a.N / 2) / (G::BN / 2) : (a.N + G::BN - 1) / G::BN;
-    a.band = tile_band(a.mblocks, a.nblocks);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_kernel<WAVES_N, WN, WM, false, MOE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) { omni_set_error("omni_moe_prefill_experts: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_tile_kernel<WAVES_N, WN, WM, false, MOE>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), G::LDS_BYTES, st, a);
-    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts");
-    return OMNI_OK;
-}
-
-bool k_moe_tile_fused_ok(int block, int I) { return I % (block == 64 ? 64 : 128) == 0; }
+// ---- the MoE prefill's expert GEMMs over the compact batch (entry points: moe_prefill.hip), in the two block heights of TILE_MOE_BLOCK
+// (tile_epi.cuh) with the K-slice order of every other geometry: bit-identical expert outputs.
+bool k_moe_tile_fused_ok(int block, int I) { return I % (block == 64 ? 64 : 128) == 0; }     // half a block's columns of gate, half of up
 
 int k_moe_tile_gemm(int mode, int block, const void* x, int64_t x_rows, int ldx, const void* w, int64_t w_expert_elems, int experts,
                     const int32_t* block_expert, const int32_t* row_token, const void* row_weight, void* out, int ldo, int rows, int N, int K,
@@ -588,12 +479,7 @@ int k_moe_tile_gemm(int mode, int block, const void* x, int64_t x_rows, int ldx,
     a.M = rows; a.N = N; a.K = K; a.act = OMNI_TILE_ACT_NONE;
     a.block_expert = block_expert; a.row_token = row_token; a.row_weight = (const uint16_t*)row_weight;
     hipStream_t st = (hipStream_t)stream;
-    if (block == 64) {
-        if (mode == MOE_GU_FUSED) return launch_tile_moe<4, 2, 2, MOE_GU_FUSED>(a, st);
-        if (mode == MOE_GU_PLAIN) return launch_tile_moe<4, 2, 2, MOE_GU_PLAIN>(a, st);
-        return launch_tile_moe<4, 2, 2, MOE_DOWN>(a, st);
-    }
-    if (mode == MOE_GU_FUSED) return launch_tile_moe<2, 8, 4, MOE_GU_FUSED>(a, st);
-    if (mode == MOE_GU_PLAIN) return launch_tile_moe<2, 8, 4, MOE_GU_PLAIN>(a, st);
-    return launch_tile_moe<2, 8, 4, MOE_DOWN>(a, st);
+    if (mode == MOE_GU_FUSED) return TILE_MOE_BLOCK(block, launch_tile, MOE_GU_FUSED, a, st);
+    if (mode == MOE_GU_PLAIN) return TILE_MOE_BLOCK(block, launch_tile, MOE_GU_PLAIN, a, st);
+    return TILE_MOE_BLOCK(block, launch_tile, MOE_DOWN, a, st);
 }

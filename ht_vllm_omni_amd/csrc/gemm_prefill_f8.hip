@@ -31,6 +31,8 @@
 // W is the MFMA's A operand: D[n][m], lane holds m = l & 15, n = 4 (l >> 4) + reg -- s_w belongs to the accumulator REGISTER, s_x to the
 // LANE; both are applied once, behind the loop, and the bf16 kernels' epilogue (tile_epi.cuh) stores the tile.
 // Every geometry adds k in the same order (one MFMA per chunk, chunks ascending): bit-identical outputs.
+// Shared with the bf16 kernels and written once in tile_epi.cuh: geometry (F8Geom), tile order, launcher, the MoE gate / up pairing and
+// finishes, the epilogue.  Which geometry a launch takes: tile_choice_fp8, gemm_tile_policy.h.
 //
 // MoE prefill on fp8 expert weights (MOE != 0 instantiations; entry point omni_moe_prefill_experts_fp8 in moe_prefill.hip): the grouped
 // gate_up and down GEMMs over the compact expert-sorted batch of omni_moe_align (one m block = 64 or 256 rows of ONE expert), on the bytes
@@ -46,9 +48,8 @@
 //      Rows with row_token < 0 and rows past the descriptor read as zero.  No VGPR staging on either operand.
 //   Arithmetic contract (include/omni_talker.h, omni_moe_prefill_experts_fp8):
 //      gate_up  g = (acc * s_x[token]) * s_w[n] in fp32 for gate and for up, act = bf16(bf16(SiLU(bf16 g_gate)) * bf16 g_up)
-//               (omni_silu_mul's three roundings, as MOE_GU_FUSED of gemm_prefill.hip); n block nb covers columns [nb BN/2, + BN/2) of gate
-//               AND of up, a wave's first WN / 2 n-tiles being gate and the second WN / 2 the same columns of up;
-//      down     y = bf16(bf16((acc * s_a[row]) * s_w[n]) * row_weight[row]) (MOE_DOWN's two roundings);
+//               (omni_silu_mul's three roundings), gate and up paired as in the bf16 kernel (tile_src_ntile, tile_moe_finish: tile_epi.cuh);
+//      down     y = bf16(bf16((acc * s_a[row]) * s_w[n]) * row_weight[row]) (MOE_DOWN's two roundings, tile_moe_finish);
 //      k order  one MFMA per chunk, ascending, in both geometries (128 x 64 for 64-row blocks, 256 x 256 for 256-row blocks).
 //   The act quantiser skips the rows of blocks without an expert (never written by gate_up; the down GEMM leaves those blocks at once);
 //   pad rows inside an expert's block are zeros: zero bytes, scale 1e-12 / 448.
@@ -56,6 +57,7 @@
 
 #include "common.cuh"
 #include "gemm_frag.cuh"
+#include "gemm_tile_policy.h"
 #include "kernels.h"
 #include "norm_row.cuh"
 #include "tile_epi.cuh"
@@ -131,6 +133,23 @@ __global__ __launch_bounds__(64 * QR_ROWS_PER_BLOCK) void quant_rows_f8_kernel(c
     }
 }
 
+// the launch: MAXV = the smallest instantiation that holds the row's K / 8 vectors, 64 lanes x MAXV (the norm prologue stops at 8: K <= 4096);
+// grid over the rows the kernel writes (pad rows included, TOK has none)
+template <bool NORM, bool TOK>
+static void quant_rows_launch(const void* x, int ldx, const void* delta, void* residual, const void* norm_w, float eps, void* q, float* scale, int M,
+                              int K, const int32_t* block_expert, int block, hipStream_t st) {
+    const dim3 grid(((TOK ? M : (M + 15) & ~15) + QR_ROWS_PER_BLOCK - 1) / QR_ROWS_PER_BLOCK);
+    const int nvec = K / 8;
+#define QR_LAUNCH(V)                                                                                                                          \
+    hipLaunchKernelGGL((quant_rows_f8_kernel<V, NORM, TOK>), grid, dim3(64 * QR_ROWS_PER_BLOCK), 0, st, (const uint16_t*)x, ldx, (const uint16_t*)delta, \
+                       (uint16_t*)residual, (const uint16_t*)norm_w, eps, (uint8_t*)q, scale, M, K, block_expert, block)
+    if (nvec <= 64 * 2) QR_LAUNCH(2);
+    else if (nvec <= 64 * 4) QR_LAUNCH(4);
+    else if (NORM || nvec <= 64 * 8) QR_LAUNCH(8);
+    else if constexpr (!NORM) QR_LAUNCH(16);
+#undef QR_LAUNCH
+}
+
 extern "C" int omni_quant_rows_fp8(const void* x, int ldx, const void* delta, void* residual, const void* norm_w, float eps, void* q_frag,
                                    float* x_scale, int M, int K, void* stream) {
     OMNI_CHECK_ARG(q_frag && x_scale && (x || residual), "omni_quant_rows_fp8: null pointer");
@@ -139,23 +158,8 @@ extern "C" int omni_quant_rows_fp8(const void* x, int ldx, const void* delta, vo
     OMNI_CHECK_ARG(!delta || residual, "omni_quant_rows_fp8: delta needs residual");
     OMNI_CHECK_ARG(residual || (ldx >= K && ldx % 8 == 0), "omni_quant_rows_fp8: ldx=%d (>= K, multiple of 8)", ldx);
     OMNI_CHECK_ARG(K <= (norm_w ? 4096 : 8192), "omni_quant_rows_fp8: K=%d too wide for a row in registers (norm prologue: 4096, plain: 8192)", K);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((((M + 15) & ~15) + QR_ROWS_PER_BLOCK - 1) / QR_ROWS_PER_BLOCK), block(64 * QR_ROWS_PER_BLOCK);
-    const int nvec = K / 8;
-#define QR_LAUNCH(V, NORM_)                                                                                                                 \
-    hipLaunchKernelGGL((quant_rows_f8_kernel<V, NORM_>), grid, block, 0, st, (const uint16_t*)x, ldx, (const uint16_t*)delta, (uint16_t*)residual, \
-                       (const uint16_t*)norm_w, eps, (uint8_t*)q_frag, x_scale, M, K)
-    if (norm_w) {
-        if (nvec <= 64 * 2) QR_LAUNCH(2, true);
-        else if (nvec <= 64 * 4) QR_LAUNCH(4, true);
-        else QR_LAUNCH(8, true);
-    } else {
-        if (nvec <= 64 * 2) QR_LAUNCH(2, false);
-        else if (nvec <= 64 * 4) QR_LAUNCH(4, false);
-        else if (nvec <= 64 * 8) QR_LAUNCH(8, false);
-        else QR_LAUNCH(16, false);
-    }
-#undef QR_LAUNCH
+    if (norm_w) quant_rows_launch<true, false>(x, ldx, delta, residual, norm_w, eps, q_frag, x_scale, M, K, nullptr, 1, (hipStream_t)stream);
+    else quant_rows_launch<false, false>(x, ldx, delta, residual, norm_w, eps, q_frag, x_scale, M, K, nullptr, 1, (hipStream_t)stream);
     OMNI_CHECK_LAUNCH("omni_quant_rows_fp8");
     return OMNI_OK;
 }
@@ -163,16 +167,7 @@ extern "C" int omni_quant_rows_fp8(const void* x, int ldx, const void* delta, vo
 int k_quant_rows_f8_tok(const void* x, int ldx, void* q, float* scale, int M, int K, const int32_t* block_expert, int block, void* stream) {
     OMNI_CHECK_ARG(x && q && scale && M >= 1 && K > 0 && K % 128 == 0 && K <= 8192 && ldx >= K && ldx % 8 == 0 && block >= 1,
                    "omni_moe_prefill_experts_fp8: quantiser M=%d K=%d ldx=%d (K %% 128 == 0, K <= 8192)", M, K, ldx);
-    const dim3 grid((M + QR_ROWS_PER_BLOCK - 1) / QR_ROWS_PER_BLOCK), block_dim(64 * QR_ROWS_PER_BLOCK);
-    const int nvec = K / 8;
-#define QR_LAUNCH(V)                                                                                                                         \
-    hipLaunchKernelGGL((quant_rows_f8_kernel<V, false, true>), grid, block_dim, 0, (hipStream_t)stream, (const uint16_t*)x, ldx, (const uint16_t*)nullptr, \
-                       (uint16_t*)nullptr, (const uint16_t*)nullptr, 0.f, (uint8_t*)q, scale, M, K, block_expert, block)
-    if (nvec <= 64 * 2) QR_LAUNCH(2);
-    else if (nvec <= 64 * 4) QR_LAUNCH(4);
-    else if (nvec <= 64 * 8) QR_LAUNCH(8);
-    else QR_LAUNCH(16);
-#undef QR_LAUNCH
+    quant_rows_launch<false, true>(x, ldx, nullptr, nullptr, nullptr, 0.f, q, scale, M, K, block_expert, block, (hipStream_t)stream);
     OMNI_CHECK_LAUNCH("omni_moe_prefill_experts_fp8(quantiser)");
     return OMNI_OK;
 }
@@ -191,23 +186,8 @@ struct F8Args {
     const int32_t* block_expert; const int32_t* row_token; const uint16_t* row_weight;
 };
 
-// 8 waves as WAVES_N x (8 / WAVES_N); a wave owns WN n-tiles x WM m-tiles of 16 x 16 (tile_epi.cuh's fragment convention)
-template <int WAVES_N, int WN, int WM>
-struct F8Geom {
-    static constexpr int WAVES_M = TG_WAVES / WAVES_N;
-    static constexpr int NTILES = WAVES_N * WN, MTILES = WAVES_M * WM;
-    static constexpr int BN = NTILES * 16, BM = MTILES * 16;
-    static constexpr int SLICE = (NTILES + MTILES) * 2048;                   // one 128-deep slice of both operands
-    static constexpr int NLW = (NTILES + TG_WAVES - 1) / TG_WAVES, NLX = (MTILES + TG_WAVES - 1) / TG_WAVES;   // chunks per wave and slice
-    static constexpr int LOADS = 2 * (NLW + NLX);                            // LDS-DMA instructions per wave and slice (uniform: counted waits)
-    static constexpr bool RAGGED = NTILES % TG_WAVES != 0 || MTILES % TG_WAVES != 0;      // some waves load zeros into a spare KB
-    static constexpr int SPARE = RAGGED ? TG_WAVES * 1024 : 0;
-    static constexpr int NBUF = (TG_LDS_MAX - SPARE) / SLICE >= 4 ? 4 : (TG_LDS_MAX - SPARE) / SLICE;
-    static constexpr int EPI_BYTES = TG_WAVES * 16 * (WN * 64 + 16);
-    static constexpr int RING_BYTES = NBUF * SLICE + SPARE;
-    static constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
-    static_assert(WN % 2 == 0 && NBUF >= 2 && (NBUF - 2) * LOADS < 64 && LDS_BYTES <= TG_LDS_MAX, "geometry");
-};
+// Geometry F8Geom<WAVES_N, WN, WM> (tile_epi.cuh): one slice = a 128-deep 2-KB chunk of every tile of both operands, two LDS-DMA
+// instructions per chunk.
 
 // one MFMA operand out of a 2-KB chunk image: a main chunk (two 1-KB blocks of 16 B per lane) or a remainder chunk (four 512-B blocks
 // of 8 B per lane); W and x chunks of one slice are of the same kind, so register e of both operands holds the same k
@@ -262,15 +242,8 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
 #pragma unroll
     for (int i = 0; i < NLW; ++i) {
         const int f = wave + TG_WAVES * i;
-        int n16 = (n0 >> 4) + f;
-        bool in_n = n16 * 16 < a.N;
-        if constexpr (MOE == MOE_GU_FUSED) {                                  // tile f = n-tile j of wave column f / WN: gate (j < WN / 2) or up
-            constexpr int HN = WN / 2;
-            const int j = f % WN;
-            const int col16 = n_blk * (NTILES / 2) + (f / WN) * HN + j % HN;  // 16-column tile of the [rows, I] output
-            in_n = col16 * 32 < a.N;
-            n16 = (j >= HN ? a.N >> 5 : 0) + col16;
-        }
+        bool in_n;
+        const int n16 = tile_src_ntile<MOE, WN, NTILES>(f, n_blk, a.N, in_n);
         wbase[i] = (f < NTILES && in_n) ? (unsigned)(n16 * tile_bytes + lane * 16) : TG_OOB;
     }
 #pragma unroll
@@ -360,9 +333,8 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the ring is dead: its tail loads (zeros) landed
 
     // ---- y = (acc * s_x[m]) * s_w[n]: the lane's m per m-tile, the register's n per n-tile.  Rows past M and columns past N are not stored
-    // (MOE: s_x belongs to the SOURCE row -- the token of a gathered row; the fused gate_up's n-tile j is gate (j < WN / 2) or up of column tile j % (WN / 2))
-    constexpr int HN = WN / 2;
-    const int mw0 = m0 + wm * WM * 16, nw0 = MOE == MOE_GU_FUSED ? n_blk * (G::BN / 2) + wn * HN * 16 : n0 + wn * WN * 16;
+    // (MOE: s_x belongs to the SOURCE row -- the token of a gathered row; s_w to the row of W that n-tile j of the wave is: tile_src_ntile)
+    const int mw0 = m0 + wm * WM * 16, nw0 = MOE == MOE_GU_FUSED ? n_blk * (G::BN / 2) + wn * (WN / 2) * 16 : n0 + wn * WN * 16;
     float sx[WM];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
@@ -372,13 +344,8 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
     }
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
-        int n = nw0 + j * 16 + 4 * q;
-        bool in_n = n < a.N;
-        if constexpr (MOE == MOE_GU_FUSED) {
-            const int col = nw0 + (j % HN) * 16 + 4 * q;
-            in_n = col < (a.N >> 1);
-            n = (j >= HN ? a.N >> 1 : 0) + col;
-        }
+        bool in_n;
+        const int n = tile_src_ntile<MOE, WN, NTILES>(wn * WN + j, n_blk, a.N, in_n) * 16 + 4 * q;
         const f32x4 sw = in_n ? *reinterpret_cast<const f32x4*>(ws + n) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < WM; ++i)
@@ -386,49 +353,28 @@ __global__ __launch_bounds__(TG_THREADS) void gemm_tile_f8_kernel(const F8Args a
             for (int e = 0; e < 4; ++e) acc[j][i][e] = (acc[j][i][e] * sx[i]) * sw[e];
     }
     TileArgs ta{};
-    ta.out = a.out; ta.ldo = a.ldo; ta.M = a.M; ta.N = a.N;
-    if constexpr (MOE == MOE_GU_FUSED) {
-        f32x4 o[HN][WM];
-#pragma unroll
-        for (int j = 0; j < HN; ++j)
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[j][i][e] = silu_mul_bf16(acc[j][i][e], acc[HN + j][i][e]);
-        ta.N = a.N >> 1;                                                      // the output's width
-        tile_epilogue<HN, WM, false, true>(ta, o, lds, wave, lane, mw0, nw0);
-    } else if constexpr (MOE == MOE_DOWN) {
-        // the two rounding points of y = bf16(acc) followed by y * weight on bf16 tensors; the lane holds row (lane & 15) of m-tile i
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            const float wgt = bf2f(a.row_weight[mw0 + i * 16 + c]);
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[j][i][e] = bfround(acc[j][i][e]) * wgt;
-        }
-        tile_epilogue<WN, WM, false, true>(ta, acc, lds, wave, lane, mw0, nw0);
-    } else {
-        tile_epilogue<WN, WM, GU8, true>(ta, acc, lds, wave, lane, mw0, nw0);
-    }
+    ta.out = a.out; ta.ldo = a.ldo; ta.M = a.M; ta.N = a.N; ta.row_weight = a.row_weight;
+    if constexpr (MOE != 0) tile_moe_finish<MOE>(ta, acc, lds, wave, lane, mw0, nw0);
+    else tile_epilogue<WN, WM, GU8, true>(ta, acc, lds, wave, lane, mw0, nw0);
 }
 
-template <int WAVES_N, int WN, int WM, bool GU8>
-static int launch_f8(F8Args a, hipStream_t st) {
-    using G = F8Geom<WAVES_N, WN, WM>;
-    a.mblocks = (a.M + G::BM - 1) / G::BM;
-    a.nblocks = (a.N + G::BN - 1) / G::BN;
-    a.band = tile_band(a.mblocks, a.nblocks);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_f8_kernel<WAVES_N, WN, WM, GU8>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) { omni_set_error("omni_gemm_tile_fp8: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
-        attr_set = true;
+template <int WAVES_N, int WN, int WM, bool GU8, int MOE = 0>
+static int launch_f8(const F8Args& a, hipStream_t st) {
+    return tile_launch_geom<gemm_tile_f8_kernel<WAVES_N, WN, WM, GU8, MOE>, F8Geom<WAVES_N, WN, WM>>(
+        a, st, MOE ? "omni_moe_prefill_experts_fp8" : "omni_gemm_tile_fp8");
+}
+
+// the instantiation a TileChoice (gemm_tile_policy.h) names
+template <bool GU8>
+static int launch_choice_f8(const TileChoice& t, const F8Args& a, hipStream_t st) {
+    switch (t.waves_n * 100 + t.wn * 10 + t.wm) {
+    case 422: return launch_f8<4, 2, 2, GU8>(a, st);
+    case 284: return launch_f8<2, 8, 4, GU8>(a, st);
+    case 447: return launch_f8<4, 4, 7, GU8>(a, st);
+    case 446: return launch_f8<4, 4, 6, GU8>(a, st);
     }
-    hipLaunchKernelGGL((gemm_tile_f8_kernel<WAVES_N, WN, WM, GU8>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), G::LDS_BYTES, st, a);
-    OMNI_CHECK_LAUNCH("omni_gemm_tile_fp8");
-    return OMNI_OK;
+    omni_set_error("omni_gemm_tile_fp8: no kernel for tile <%d, %d, %d>", t.waves_n, t.wn, t.wm);
+    return OMNI_EINVAL;
 }
 
 extern "C" int omni_gemm_tile_fp8(const omni_tile_gemm_fp8* g, void* stream) {
@@ -444,48 +390,12 @@ extern "C" int omni_gemm_tile_fp8(const omni_tile_gemm_fp8* g, void* stream) {
     F8Args a{};
     a.x8 = (const uint8_t*)g->x8; a.xs = g->x_scale; a.W = (const uint8_t*)g->w8; a.ws = g->w_scale;
     a.out = (uint16_t*)g->out; a.ldo = g->ldo; a.M = g->M; a.N = g->N; a.K = g->K;
-    hipStream_t st = (hipStream_t)stream;
-    // the 128 x 64 tile where 256-column tiles do not divide N or would leave most of the 256 CUs idle (the bf16 dispatch's rule)
-    const long long big_tiles = (long long)((g->N + 255) / 256) * ((g->M + 255) / 256);
-    if (g->tile_hint == 2 || g->N % 256 != 0 || (g->tile_hint == 0 && big_tiles < 96))
-        return gu8 ? launch_f8<4, 2, 2, true>(a, st) : launch_f8<4, 2, 2, false>(a, st);
-    // 256 columns x 256 / 224 / 192 rows: one workgroup per CU, a grid runs in rounds of 256 tiles and a round costs ~ the tile's rows
-    int bm = 256;
-    if (g->tile_hint == 3) bm = 224;
-    else if (g->tile_hint == 4) bm = 192;
-    else if (g->tile_hint == 0) {
-        long long best = -1;
-        for (int cand : {256, 224, 192}) {
-            const long long tiles = (long long)((g->M + cand - 1) / cand) * (g->N / 256);
-            const long long cost = ((tiles + 255) / 256) * (cand + 16);
-            if (best < 0 || cost < best) { best = cost; bm = cand; }
-        }
-    }
-    if (bm == 224) return gu8 ? launch_f8<4, 4, 7, true>(a, st) : launch_f8<4, 4, 7, false>(a, st);
-    if (bm == 192) return gu8 ? launch_f8<4, 4, 6, true>(a, st) : launch_f8<4, 4, 6, false>(a, st);
-    return gu8 ? launch_f8<2, 8, 4, true>(a, st) : launch_f8<2, 8, 4, false>(a, st);
+    const TileChoice t = tile_choice_fp8(g->M, g->N, g->tile_hint);
+    return gu8 ? launch_choice_f8<true>(t, a, (hipStream_t)stream) : launch_choice_f8<false>(t, a, (hipStream_t)stream);
 }
 
-// ---- the MoE prefill's expert GEMMs on fp8 weights over the compact batch (entry point: moe_prefill.hip).  Two block heights, the same k
-// order: 64 rows = <4, 2, 2> (128 columns; gate_up: 64 gate + 64 up), 256 rows = <2, 8, 4> (256 columns; gate_up: 128 + 128).
-template <int WAVES_N, int WN, int WM, int MOE>
-static int launch_f8_moe(F8Args a, hipStream_t st) {
-    using G = F8Geom<WAVES_N, WN, WM>;
-    a.mblocks = a.M / G::BM;
-    a.nblocks = MOE == MOE_GU_FUSED ? (a.N / 2) / (G::BN / 2) : (a.N + G::BN - 1) / G::BN;
-    a.band = tile_band(a.mblocks, a.nblocks);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tile_f8_kernel<WAVES_N, WN, WM, false, MOE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) { omni_set_error("omni_moe_prefill_experts_fp8: LDS attribute: %s", hipGetErrorString(e)); return OMNI_EHIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_tile_f8_kernel<WAVES_N, WN, WM, false, MOE>), dim3(a.mblocks * a.nblocks), dim3(TG_THREADS), G::LDS_BYTES, st, a);
-    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts_fp8");
-    return OMNI_OK;
-}
-
+// ---- the MoE prefill's expert GEMMs on fp8 weights over the compact batch (entry point: moe_prefill.hip), in the two block heights of
+// TILE_MOE_BLOCK (tile_epi.cuh), the same k order in both.
 int k_moe_tile_gemm_f8(int mode, int block, const void* x8, const float* x_scale, int x_rows, const void* w8, const float* w_scale, int experts,
                        const int32_t* block_expert, const int32_t* row_token, const void* row_weight, void* out, int ldo, int rows, int N, int K,
                        void* stream) {
@@ -502,6 +412,6 @@ int k_moe_tile_gemm_f8(int mode, int block, const void* x8, const float* x_scale
     a.out = (uint16_t*)out; a.ldo = ldo; a.M = rows; a.N = N; a.K = K;
     a.block_expert = block_expert; a.row_token = row_token; a.row_weight = (const uint16_t*)row_weight;
     hipStream_t st = (hipStream_t)stream;
-    if (block == 64) return mode == MOE_GU_FUSED ? launch_f8_moe<4, 2, 2, MOE_GU_FUSED>(a, st) : launch_f8_moe<4, 2, 2, MOE_DOWN>(a, st);
-    return mode == MOE_GU_FUSED ? launch_f8_moe<2, 8, 4, MOE_GU_FUSED>(a, st) : launch_f8_moe<2, 8, 4, MOE_DOWN>(a, st);
+    if (mode == MOE_GU_FUSED) return TILE_MOE_BLOCK(block, launch_f8, MOE_GU_FUSED, a, st);
+    return TILE_MOE_BLOCK(block, launch_f8, MOE_DOWN, a, st);
 }

@@ -1,7 +1,11 @@
-// Tile policy of the skinny GEMM: which workgroup tile (NT 16-row n-tiles x MT 16-row m-tiles) and how many M splits a launch takes.
-// Pure host arithmetic on (norm, epilogue, M, N, K) with no HIP dependency: gemm.hip and gemm_w8.hip both call it (the bf16 kernel's bits
-// depend on the row tile only through SlabOrder, the W8 kernel's not at all -- its time does), the persistent chains are built for the tiles
-// it gives at 64 rows, and tests/test_gemm_tile_policy.py holds it to a table on the CPU.
+// Tile policies of the GEMMs, as pure host arithmetic with no HIP dependency, each held to a table on the CPU (tests/test_gemm_tile_policy.py,
+// tests/test_gemm_tile_choice.py): a tile changes time, never bits (or bits in a way the kernels' own tests pin), so no GPU test sees it drift.
+//   skinny_tile_*   the skinny (decode) GEMM: which workgroup tile (NT 16-row n-tiles x MT 16-row m-tiles) and how many M splits a launch takes,
+//                   on (norm, epilogue, M, N, K).  gemm.hip and gemm_w8.hip both call it (the bf16 kernel's bits depend on the row tile only
+//                   through SlabOrder, the W8 kernel's not at all -- its time does); the persistent chains are built for the tiles it gives
+//                   at 64 rows.
+//   tile_choice_*   the tile (prefill) GEMM: which geometry and kernel form omni_gemm_tile (gemm_prefill.hip) and omni_gemm_tile_fp8
+//                   (gemm_prefill_f8.hip) run; at the end of this file.
 //
 // Plain GEMMs: narrow n groups (NT = 1, SiLU 16 + 16 columns), M split over grid.y until the grid has ~`wgs` workgroups.  Norm-fused
 // (PRO_XNORM, and its deferred-rstd form): wide n groups (NT = 4) and as many M splits as that allows -- the normalisation work of a
@@ -57,4 +61,63 @@ static inline void skinny_tile_mt(bool norm, int epi, int M, int N, int nt, int 
     if (splits < 1) splits = 1;
     *mt_out = (mt_total + splits - 1) / splits;
     *splits_out = skinny_tile_splits(M, mt_out);
+}
+
+// ---- the tile GEMM.  A choice is a geometry <waves along n, n-tiles per wave, m-tiles per wave> of the lock-step kernel: 256 x 256 <2, 8, 4> |
+// 256 x 224 <4, 4, 7> | 256 x 192 <4, 4, 6> | 192 x 256 <2, 6, 4> | 128 x 512 <1, 8, 4> | 96 x 512 <1, 6, 4> (columns x rows) and the small
+// 128 x 64 <4, 2, 2>; or, mw != 0, the two-group form of the 256-column tile with 32 mw rows (gemm_tile_pp_kernel<MW>; bf16 only).  Every
+// geometry adds k in the same order: the choice never changes a bit of the output.
+struct TileChoice { int waves_n, wn, wm, mw; };
+#define TILE_CUS 256              // workgroups of one round: one per CU (the ring takes most of the LDS)
+#define TILE_FEW 96               // fewer big tiles than this leave most CUs idle: the K loop's latency is the cost, not MFMA throughput
+
+static inline long long tile_count(int M, int N, int bm, int bn) { return (long long)((N + bn - 1) / bn) * ((M + bm - 1) / bm); }
+
+// 256-column tiles come in three heights.  A grid runs in rounds of TILE_CUS tiles and a round costs ~ the tile's rows: 6.4 k prompt tokens
+// x 2048 columns are 208 tiles of 256 rows (one round, 48 CUs idle) or 232 tiles of 224 rows (one round, 12.5 % shorter)
+static inline int tile_rows_by_rounds(int M, int N) {
+    long long best = -1;
+    int bm = 256;
+    for (int cand = 256; cand >= 192; cand -= 32) {           // ties go to the taller tile
+        const long long cost = ((tile_count(M, N, cand, 256) + TILE_CUS - 1) / TILE_CUS) * (cand + 16);
+        if (best < 0 || cost < best) { best = cost; bm = cand; }
+    }
+    return bm;
+}
+
+// rows of the 256-column tile: tile_hint 3 / 4 name 224 / 192, else by rounds where `by_rounds`, else 256
+static inline int tile_rows_256(int M, int N, int hint, bool by_rounds) {
+    if (hint == 3) return 224;
+    if (hint == 4) return 192;
+    return by_rounds ? tile_rows_by_rounds(M, N) : 256;
+}
+
+static inline TileChoice tile_lockstep_256(int bm) { return bm == 224 ? TileChoice{4, 4, 7, 0} : (bm == 192 ? TileChoice{4, 4, 6, 0} : TileChoice{2, 8, 4, 0}); }
+
+// omni_gemm_tile.  `plain` = no conv window, no groups, no group_rows: what the two-group form takes (5 - 8 % faster at every height).
+// tile_hint: 0 auto | 1 big lock-step | 2 small | 3 / 4 lock-step 224 / 192 rows | 5 / 6 / 7 two-group 256 / 224 / 192 rows.
+static inline TileChoice tile_choice_bf16(int M, int N, int groups, bool plain, bool gu8, int hint) {
+    // the small tile for problems whose big-tile grid would leave most CUs idle (the Code2Wav transformer / ConvNeXt at a few hundred frames,
+    // streaming chunks); the big tile is the widest that divides N
+    const int big_n = N % 256 == 0 ? 256 : (N % 192 == 0 ? 192 : (N % 128 == 0 ? 128 : (N % 96 == 0 ? 96 : (N > 128 ? 256 : 128))));
+    const int big_m = big_n >= 192 ? 256 : 512;
+    if (hint == 2 || (hint == 0 && tile_count(M, N, big_m, big_n) * groups < TILE_FEW && N >= 64)) return {4, 2, 2, 0};
+    if (N % 256 == 0) {
+        const int h = hint == 5 ? 1 : (hint > 5 ? hint - 3 : hint);       // 5 / 6 / 7 name the heights of 1 / 3 / 4
+        const int bm = tile_rows_256(M, N, h, hint == 0 && groups == 1);
+        if (hint >= 5 || (hint == 0 && plain)) return {4, 4, 0, bm / 32};
+        return tile_lockstep_256(bm);
+    }
+    if (gu8) return {1, 8, 4, 0};
+    if (N % 192 == 0) return {2, 6, 4, 0};
+    if (N % 128 == 0) return {1, 8, 4, 0};
+    if (N % 96 == 0) return {1, 6, 4, 0};
+    return N > 128 ? TileChoice{2, 8, 4, 0} : TileChoice{1, 8, 4, 0};
+}
+
+// omni_gemm_tile_fp8.  The small tile where 256-column tiles do not divide N or would leave most CUs idle; tile_hint: 0 auto | 1 256 rows |
+// 2 small | 3 / 4 224 / 192 rows.
+static inline TileChoice tile_choice_fp8(int M, int N, int hint) {
+    if (hint == 2 || N % 256 != 0 || (hint == 0 && tile_count(M, N, 256, 256) < TILE_FEW)) return {4, 2, 2, 0};
+    return tile_lockstep_256(tile_rows_256(M, N, hint, hint == 0));
 }

@@ -138,10 +138,11 @@ bool k_bb_engine_enabled();
 int k_bb_engine(const omni_layer_weights& w, const omni_layer_weights* next, const void* attn, void* resid, float* part, void* act, void* qkv,
                 int B, float eps, uint32_t* flags, int32_t* err, void* stream);
 // the MoE prefill's expert GEMMs (gemm_prefill.hip, instantiations of gemm_tile_kernel) over the expert-sorted compact batch that
-// moe_prefill.hip's alignment kernels lay out: `rows` batch rows in blocks of `block` (64 | 256) rows, block b owned by expert
-// block_expert[b] (< 0: none) whose matrix is w + expert * w_expert_elems (fragment-major [N, K]).
+// moe_prefill.hip's alignment kernels lay out: `rows` batch rows in blocks of `block` (64 | 256) rows (their geometries: TILE_MOE_BLOCK,
+// tile_epi.cuh), block b owned by expert block_expert[b] (< 0: none) whose matrix is w + expert * w_expert_elems (fragment-major [N, K]).
 //   MOE_GU_FUSED: x [x_rows, ldx] gathered through row_token, w = [gate rows | up rows] (N = 2 I), out = act [rows, I] (SiLU(gate) * up in registers)
 //   MOE_GU_PLAIN: the same gather, out = [rows, N]            MOE_DOWN: x = act [rows, K], out = bf16(bf16(acc) * row_weight[row])
+// (the gate / up pairing and the two finishes, for bf16 and fp8 experts alike: tile_src_ntile and tile_moe_finish, tile_epi.cuh)
 #define MOE_GU_FUSED 1
 #define MOE_GU_PLAIN 2
 #define MOE_DOWN 3

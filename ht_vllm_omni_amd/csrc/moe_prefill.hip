@@ -17,8 +17,9 @@
 // list twice, from L2.
 // Two launches because an expert's start needs every other expert's count.
 //
-// Expert GEMMs: gemm_prefill.hip (gemm_tile_kernel's MOE instantiations).  Combine: one workgroup per token reads its k rows of y through
-// slot_row, 8 columns per thread.
+// Expert GEMMs: the MOE instantiations of the tile kernels of gemm_prefill.hip (bf16 experts) and gemm_prefill_f8.hip (fp8 experts); what
+// the two share -- the gate / up pairing, the finishes, the block heights -- is in tile_epi.cuh.  Combine: one workgroup per token reads its
+// k rows of y through slot_row, 8 columns per thread.
 #include "common.cuh"
 #include "kernels.h"
 
@@ -180,19 +181,35 @@ extern "C" int omni_moe_align(const omni_moe_align_args* g, void* stream) {
     return OMNI_OK;
 }
 
-extern "C" int omni_moe_prefill_experts(const omni_moe_prefill_args* g, void* stream) {
+// What the two entry points have in common (G = omni_moe_prefill_args | omni_moe_prefill_fp8_args): the checks on the fields both structs hold ...
+template <typename G>
+static int moe_prefill_check(const G* g, const char* name) {
     OMNI_CHECK_ARG(g && g->x && g->topk_idx && g->block_expert && g->row_token && g->row_weight && g->slot_row && g->w_gate_up && g->w_down &&
-                   g->act_ws && g->y_ws && g->out, "omni_moe_prefill_experts: null argument");
+                   g->act_ws && g->y_ws && g->out, "%s: null argument", name);
     OMNI_CHECK_ARG(g->T >= 1 && g->top_k >= 1 && g->top_k <= MP_MAXK && g->E_local >= 1 && g->E_local <= MP_MAXE,
-                   "omni_moe_prefill_experts: T=%d top_k=%d E_local=%d", g->T, g->top_k, g->E_local);
+                   "%s: T=%d top_k=%d E_local=%d", name, g->T, g->top_k, g->E_local);
+    OMNI_CHECK_ARG(g->block == 64 || g->block == 256, "%s: block=%d (64 | 256)", name, g->block);
+    OMNI_CHECK_ARG(g->r_max == moe_r_max(g->T, g->top_k, g->E_local, g->block), "%s: r_max=%d does not belong to these sizes", name, g->r_max);
+    OMNI_CHECK_ARG(!g->shared || (g->gate_logit && g->ld_gate >= 1), "%s: shared expert output without its gate logits", name);
+    return OMNI_OK;
+}
+
+// ... and the combine behind the down GEMM
+template <typename G>
+static int launch_combine(const G* g, void* stream, const char* name) {
+    hipLaunchKernelGGL(moe_prefill_combine_kernel, dim3(g->T), dim3(128), 0, (hipStream_t)stream, (const uint16_t*)g->y_ws, g->topk_idx,
+                       g->slot_row, (const uint16_t*)g->shared, (const uint16_t*)g->gate_logit, g->ld_gate, (uint16_t*)g->out, g->top_k, g->H);
+    OMNI_CHECK_LAUNCH(name);
+    return OMNI_OK;
+}
+
+extern "C" int omni_moe_prefill_experts(const omni_moe_prefill_args* g, void* stream) {
+    int rc = moe_prefill_check(g, "omni_moe_prefill_experts");
+    if (rc != OMNI_OK) return rc;
     OMNI_CHECK_ARG(g->H > 0 && g->H % 64 == 0 && g->I > 0 && g->I % 32 == 0, "omni_moe_prefill_experts: H=%d I=%d (H %% 64, I %% 32)", g->H, g->I);
-    OMNI_CHECK_ARG(g->block == 64 || g->block == 256, "omni_moe_prefill_experts: block=%d (64 | 256)", g->block);
-    OMNI_CHECK_ARG(g->r_max == moe_r_max(g->T, g->top_k, g->E_local, g->block), "omni_moe_prefill_experts: r_max=%d does not belong to these sizes", g->r_max);
-    OMNI_CHECK_ARG(!g->shared || (g->gate_logit && g->ld_gate >= 1), "omni_moe_prefill_experts: shared expert output without its gate logits");
     const int H = g->H, I = g->I, R = g->r_max;
     const bool fused = k_moe_tile_fused_ok(g->block, I);
     OMNI_CHECK_ARG(fused || g->gu_ws, "omni_moe_prefill_experts: I=%d takes the unfused gate_up path, which needs gu_ws", I);
-    int rc;
     if (fused) {
         rc = k_moe_tile_gemm(MOE_GU_FUSED, g->block, g->x, g->T, H, g->w_gate_up, (int64_t)2 * I * H, g->E_local, g->block_expert, g->row_token,
                              nullptr, g->act_ws, I, R, 2 * I, H, stream);
@@ -207,26 +224,18 @@ extern "C" int omni_moe_prefill_experts(const omni_moe_prefill_args* g, void* st
     rc = k_moe_tile_gemm(MOE_DOWN, g->block, g->act_ws, R, I, g->w_down, (int64_t)H * I, g->E_local, g->block_expert, nullptr, g->row_weight,
                          g->y_ws, H, R, H, I, stream);
     if (rc != OMNI_OK) return rc;
-    hipLaunchKernelGGL(moe_prefill_combine_kernel, dim3(g->T), dim3(128), 0, (hipStream_t)stream, (const uint16_t*)g->y_ws, g->topk_idx,
-                       g->slot_row, (const uint16_t*)g->shared, (const uint16_t*)g->gate_logit, g->ld_gate, (uint16_t*)g->out, g->top_k, H);
-    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts(combine)");
-    return OMNI_OK;
+    return launch_combine(g, stream, "omni_moe_prefill_experts(combine)");
 }
 
 // The same block on the decode step's fp8 expert bytes (gemm_prefill_f8.hip: the fp8 MFMA, W8A8): quantise the token rows once, gathered
 // gate_up GEMM, quantise the act rows of the blocks an expert owns, down GEMM, the unchanged combine.  No host read.
 extern "C" int omni_moe_prefill_experts_fp8(const omni_moe_prefill_fp8_args* g, void* stream) {
-    OMNI_CHECK_ARG(g && g->x && g->topk_idx && g->block_expert && g->row_token && g->row_weight && g->slot_row && g->w_gate_up && g->s_gate_up &&
-                   g->w_down && g->s_down && g->x8_ws && g->xs_ws && g->act_ws && g->a8_ws && g->as_ws && g->y_ws && g->out,
-                   "omni_moe_prefill_experts_fp8: null argument");
-    OMNI_CHECK_ARG(g->T >= 1 && g->top_k >= 1 && g->top_k <= MP_MAXK && g->E_local >= 1 && g->E_local <= MP_MAXE,
-                   "omni_moe_prefill_experts_fp8: T=%d top_k=%d E_local=%d", g->T, g->top_k, g->E_local);
+    int rc = moe_prefill_check(g, "omni_moe_prefill_experts_fp8");
+    if (rc != OMNI_OK) return rc;
+    OMNI_CHECK_ARG(g->s_gate_up && g->s_down && g->x8_ws && g->xs_ws && g->a8_ws && g->as_ws, "omni_moe_prefill_experts_fp8: null argument");
     OMNI_CHECK_ARG(g->H > 0 && g->H % 128 == 0 && g->I > 0 && g->I % 128 == 0, "omni_moe_prefill_experts_fp8: H=%d I=%d (H %% 128, I %% 128)", g->H, g->I);
-    OMNI_CHECK_ARG(g->block == 64 || g->block == 256, "omni_moe_prefill_experts_fp8: block=%d (64 | 256)", g->block);
-    OMNI_CHECK_ARG(g->r_max == moe_r_max(g->T, g->top_k, g->E_local, g->block), "omni_moe_prefill_experts_fp8: r_max=%d does not belong to these sizes", g->r_max);
-    OMNI_CHECK_ARG(!g->shared || (g->gate_logit && g->ld_gate >= 1), "omni_moe_prefill_experts_fp8: shared expert output without its gate logits");
     const int H = g->H, I = g->I, R = g->r_max;
-    int rc = k_quant_rows_f8_tok(g->x, H, g->x8_ws, g->xs_ws, g->T, H, nullptr, 1, stream);
+    rc = k_quant_rows_f8_tok(g->x, H, g->x8_ws, g->xs_ws, g->T, H, nullptr, 1, stream);
     if (rc != OMNI_OK) return rc;
     rc = k_moe_tile_gemm_f8(MOE_GU_FUSED, g->block, g->x8_ws, g->xs_ws, g->T, g->w_gate_up, g->s_gate_up, g->E_local, g->block_expert, g->row_token,
                             nullptr, g->act_ws, I, R, 2 * I, H, stream);
@@ -236,8 +245,5 @@ extern "C" int omni_moe_prefill_experts_fp8(const omni_moe_prefill_fp8_args* g, 
     rc = k_moe_tile_gemm_f8(MOE_DOWN, g->block, g->a8_ws, g->as_ws, R, g->w_down, g->s_down, g->E_local, g->block_expert, nullptr, g->row_weight,
                             g->y_ws, H, R, H, I, stream);
     if (rc != OMNI_OK) return rc;
-    hipLaunchKernelGGL(moe_prefill_combine_kernel, dim3(g->T), dim3(128), 0, (hipStream_t)stream, (const uint16_t*)g->y_ws, g->topk_idx,
-                       g->slot_row, (const uint16_t*)g->shared, (const uint16_t*)g->gate_logit, g->ld_gate, (uint16_t*)g->out, g->top_k, H);
-    OMNI_CHECK_LAUNCH("omni_moe_prefill_experts_fp8(combine)");
-    return OMNI_OK;
+    return launch_combine(g, stream, "omni_moe_prefill_experts_fp8(combine)");
 }

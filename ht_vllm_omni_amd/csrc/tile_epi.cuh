@@ -1,9 +1,17 @@
 // What the tile GEMMs share: gemm_tile_kernel / gemm_tile_pp_kernel (gemm_prefill.hip, bf16 operands) and gemm_tile_f8_kernel
-// (gemm_prefill_f8.hip, fp8 operands).  All of them end with D[n][m] accumulator fragments of v_mfma_*_16x16x*: the launch arguments,
-// the order in which workgroups take output tiles, and the epilogue (transposed store through LDS, the GU8 SiLU * up pairing) live here.
+// (gemm_prefill_f8.hip, fp8 operands).  All of them end with D[n][m] accumulator fragments of v_mfma_*_16x16x*.  Here, once each:
+//   TileArgs, tile_launch                 the launch arguments and "set the LDS attribute once, launch, check";
+//   TileGeomT (TileGeom / F8Geom)         waves x tiles -> block, slice, ring and LDS sizes, pinned per instantiated geometry;
+//   tile_block / tile_band                the order in which workgroups take output tiles;
+//   tile_src_ntile                        which 16 rows of W an n-tile of the block is (the MoE fused gate_up pairing);
+//   tile_moe_finish                       the MoE prefill's two finishes (SiLU(gate) * up; bf16(acc) * routing weight);
+//   tile_epilogue                         the transposed store through LDS with the GU8 SiLU * up pairing.
+// What differs for real between the operand widths -- staging, rings, counted waits, MFMA loops -- stays in the two .hip files; which
+// geometry a launch takes is host arithmetic in gemm_tile_policy.h.
 #pragma once
 #include "common.cuh"
 #include "gemm_frag.cuh"
+#include "kernels.h"
 
 #define TG_WAVES 8
 #define TG_THREADS (TG_WAVES * 64)
@@ -34,6 +42,48 @@ struct TileArgs {
     const int32_t* block_expert; const int32_t* row_token; const uint16_t* row_weight;
 };
 
+// Geometry of one instantiation: 8 waves (two per SIMD: while one issues its LDS-DMA pieces -- 60 - 180 cycles each -- or waits for
+// fragments, the other feeds the matrix pipe) as WAVES_N x (8 / WAVES_N); a wave owns WN n-tiles x WM m-tiles of 16 x 16 (acc = WN * WM * 4
+// of its 256 registers); BN = WAVES_N * WN * 16, BM = (8 / WAVES_N) * WM * 16.  A slice holds one CHUNK (bytes of a 16-row tile per MFMA
+// depth: 1 KB = 32 k of bf16, 2 KB = 128 k of fp8) of every tile of both operands, staged by DMA LDS-DMA instructions per chunk.
+template <int CHUNK, int DMA, int WAVES_N, int WN, int WM>
+struct TileGeomT {
+    static constexpr int WAVES_M = TG_WAVES / WAVES_N;
+    static constexpr int NTILES = WAVES_N * WN, MTILES = WAVES_M * WM;
+    static constexpr int BN = NTILES * 16, BM = MTILES * 16;
+    static constexpr int SLICE = (NTILES + MTILES) * CHUNK;
+    static constexpr int NLW = (NTILES + TG_WAVES - 1) / TG_WAVES, NLX = (MTILES + TG_WAVES - 1) / TG_WAVES;   // chunks per wave and slice
+    static constexpr int LOADS = DMA * (NLW + NLX);                          // LDS-DMA instructions per wave and slice (uniform: counted waits)
+    static constexpr bool W_RAGGED = NTILES % TG_WAVES != 0;                 // some waves issue a dummy W load into a spare KB (uniform counts)
+    static constexpr bool X_RAGGED = MTILES % TG_WAVES != 0;                 // likewise for x
+    static constexpr int SPARE = W_RAGGED || X_RAGGED ? TG_WAVES * 1024 : 0;
+    static constexpr int FLOOR = (TG_LDS_MAX - SPARE) / SLICE;               // slices that fit
+    static constexpr int NBUF = FLOOR >= 4 ? 4 : FLOOR;                      // the ring: min(4, floor), at least 2
+    static constexpr int EPI_BYTES = TG_WAVES * 16 * (WN * 64 + 16);         // fp32 image of one m-tile x the wave's columns
+    static constexpr int RING_BYTES = NBUF * SLICE + SPARE;
+    static constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
+    static_assert(WN % 2 == 0 && NBUF >= 2 && (NBUF - 2) * LOADS < 64 && LDS_BYTES <= TG_LDS_MAX, "geometry");
+};
+template <int WAVES_N, int WN, int WM> using TileGeom = TileGeomT<1024, 1, WAVES_N, WN, WM>;      // bf16: gemm_tile_kernel
+template <int WAVES_N, int WN, int WM> using F8Geom = TileGeomT<2048, 2, WAVES_N, WN, WM>;        // fp8: gemm_tile_f8_kernel
+// Every instantiated geometry, pinned to the figures of the two structs this template replaced: a ring that outgrows them is an LDS
+// overrun, a load count that drifts is a counted wait that lets a slice be read before it landed.  (SLICE, NBUF, LOADS, LDS_BYTES)
+#define TG_PIN(GEOM, A, B, C, slice, nbuf, loads, lds)                                                                                 \
+    static_assert(GEOM<A, B, C>::SLICE == slice && GEOM<A, B, C>::NBUF == nbuf && GEOM<A, B, C>::LOADS == loads && GEOM<A, B, C>::LDS_BYTES == lds, \
+                  "tile geometry moved: " #GEOM "<" #A ", " #B ", " #C ">")
+TG_PIN(TileGeom, 2, 8, 4, 32768, 4, 4, 131072);
+TG_PIN(TileGeom, 4, 4, 7, 30720, 4, 4, 131072);
+TG_PIN(TileGeom, 4, 4, 6, 28672, 4, 4, 122880);
+TG_PIN(TileGeom, 4, 2, 2, 12288, 4, 2, 57344);
+TG_PIN(TileGeom, 1, 8, 4, 40960, 4, 5, 163840);
+TG_PIN(TileGeom, 2, 6, 4, 28672, 4, 4, 122880);
+TG_PIN(TileGeom, 1, 6, 4, 38912, 4, 5, 163840);
+TG_PIN(F8Geom, 2, 8, 4, 65536, 2, 8, 131072);
+TG_PIN(F8Geom, 4, 4, 7, 61440, 2, 8, 131072);
+TG_PIN(F8Geom, 4, 4, 6, 57344, 2, 8, 122880);
+TG_PIN(F8Geom, 4, 2, 2, 24576, 4, 4, 106496);
+#undef TG_PIN
+
 // The (n block, m block) of this workgroup.  XCD-aware tile order (bijective for any grid size): the hardware deals workgroup ids
 // round-robin over the 8 XCDs, so id -> a contiguous chunk of the tile order per XCD.  Tile order: bands of `band` m blocks, n-major inside
 // a band, so that an XCD's contiguous chunk of ~nwg / 8 tiles is a compact 2-D block (~sqrt x sqrt) of the tile grid: it touches the
@@ -55,6 +105,52 @@ static inline int tile_band(int mblocks, int nblocks) {
     int band = 1;
     while (band * band < per_xcd) ++band;
     return band > mblocks ? mblocks : band;
+}
+
+// One launch of tile kernel KERNEL (Args = TileArgs | F8Args): the dynamic-LDS attribute once per kernel, the launch, its check.
+template <auto KERNEL, typename Args>
+static int tile_launch(dim3 grid, int lds_bytes, const Args& a, hipStream_t st, const char* name) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) { omni_set_error("%s: LDS attribute: %s", name, hipGetErrorString(e)); return OMNI_EHIP; }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(KERNEL, grid, dim3(TG_THREADS), lds_bytes, st, a);
+    OMNI_CHECK_LAUNCH(name);
+    return OMNI_OK;
+}
+
+// ... of a lock-step kernel of geometry G over a.M rows x a.N rows of W (the MoE fused gate_up: N / 2 output columns in blocks of BN / 2,
+// which divide them -- the same count), `groups` of them along grid.y
+template <auto KERNEL, typename G, typename Args>
+static int tile_launch_geom(Args a, hipStream_t st, const char* name, int groups = 1) {
+    a.mblocks = (a.M + G::BM - 1) / G::BM;
+    a.nblocks = (a.N + G::BN - 1) / G::BN;
+    a.band = tile_band(a.mblocks, a.nblocks);
+    return tile_launch<KERNEL>(dim3(a.mblocks * a.nblocks, groups), G::LDS_BYTES, a, st, name);
+}
+
+// The MoE prefill's two block heights, one m block = `block` rows of ONE expert: 64 rows = <4, 2, 2> (128 columns; fused: 64 gate + 64 up),
+// 256 rows = <2, 8, 4> (256 columns; fused: 128 + 128).  LAUNCH<WAVES_N, WN, WM, GU8, MOE>(...) is the caller's launcher.
+#define TILE_MOE_BLOCK(block, LAUNCH, MOE, ...) ((block) == 64 ? LAUNCH<4, 2, 2, false, MOE>(__VA_ARGS__) : LAUNCH<2, 8, 4, false, MOE>(__VA_ARGS__))
+
+// Which 16 rows of W tile f of a workgroup's NTILES n-tiles is (f = wave column * WN + the wave's n-tile j), and whether it lies inside the
+// N rows.  Plain: n block and tile in order.  MOE_GU_FUSED (W = [gate rows | up rows], N = 2 I): n block nb covers columns [nb BN/2, + BN/2)
+// of gate AND of up, a wave's first WN / 2 n-tiles being gate and its second WN / 2 the SAME columns of up, so that gate and up of an output
+// element meet in one lane.  W staging of both kernels and the fp8 kernel's row scales go through here.
+template <int MOE, int WN, int NTILES>
+__device__ __forceinline__ int tile_src_ntile(int f, int n_blk, int N, bool& in_n) {
+    int n16 = n_blk * NTILES + f;
+    in_n = n16 * 16 < N;
+    if constexpr (MOE == MOE_GU_FUSED) {
+        constexpr int HN = WN / 2;
+        const int j = f % WN;
+        const int col16 = n_blk * (NTILES / 2) + (f / WN) * HN + j % HN;      // 16-column tile of the [rows, I] output
+        in_n = col16 * 32 < N;
+        n16 = (j >= HN ? N >> 5 : 0) + col16;
+    }
+    return n16;
 }
 
 __device__ __forceinline__ float tg_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
@@ -202,5 +298,38 @@ __device__ __forceinline__ void tile_epilogue(const TileArgs& a, f32x4 (&acc)[WN
             }
         }
         __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// The finishes of the MoE prefill's expert GEMMs (MOE = MOE_GU_FUSED | MOE_GU_PLAIN | MOE_DOWN, kernels.h) on this wave's accumulators, whose
+// row 16 i + (lane & 15) of the block's rows from mw0 the lane holds; a.N = the rows of W, nw0 = the wave's first OUTPUT column.
+//   MOE_GU_FUSED  n-tile j is gate and HN + j up of the same columns: act = bf16(bf16(SiLU(bf16 gate)) * bf16 up) (silu_mul_bf16) [rows, N / 2];
+//   MOE_DOWN      the two rounding points of y = bf16(acc) followed by y * weight on bf16 tensors, weight = a.row_weight[row];
+//   MOE_GU_PLAIN  the accumulators as they are.
+template <int MOE, int WN, int WM>
+__device__ __forceinline__ void tile_moe_finish(TileArgs a, f32x4 (&acc)[WN][WM], uint8_t* lds, int wave, int lane, int mw0, int nw0) {
+    if constexpr (MOE == MOE_GU_FUSED) {
+        constexpr int HN = WN / 2;
+        f32x4 o[HN][WM];
+#pragma unroll
+        for (int j = 0; j < HN; ++j)
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[j][i][e] = silu_mul_bf16(acc[j][i][e], acc[HN + j][i][e]);
+        a.N >>= 1;                                                            // the output's width
+        tile_epilogue<HN, WM, false, true>(a, o, lds, wave, lane, mw0, nw0);
+    } else {
+        if constexpr (MOE == MOE_DOWN) {
+#pragma unroll
+            for (int i = 0; i < WM; ++i) {
+                const float wgt = bf2f(a.row_weight[mw0 + i * 16 + (lane & 15)]);
+#pragma unroll
+                for (int j = 0; j < WN; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[j][i][e] = bfround(acc[j][i][e]) * wgt;
+            }
+        }
+        tile_epilogue<WN, WM, false, true>(a, acc, lds, wave, lane, mw0, nw0);
     }
 }
